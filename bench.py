@@ -10,7 +10,7 @@ Workloads (BASELINE.json configs; --config picks the preset, single flags overri
   c3            YOLOv3 (fp32, letterbox + Darknet53 + decode + NMS on device) + FaceNet, det-batch 32.
   c4            ViT-L/16 encoder only, enc-batch 128 over pre-cropped 224x224 faces in HBM; one step
                 = one enc-batch per GPU.
-  c5            YOLOv3 + ViT-L/16 on 1080p frames; after the timed detect+encode region, the
+  c5            YOLOv3 + ViT-L/16 on 1080p frames; with --full, after the timed detect+encode region, the
                 gathered embeddings go through the cosine dedupe and the K-means k=2..16 sweep
                 sharded by k across ranks (timed separately: `grouping`).
 The timed region ends with the RCCL all-gather-v of every rank's embeddings (the exchange step
@@ -19,7 +19,13 @@ before grouping).  value = faces encoded by all ranks / max-over-ranks wall time
 per-lane encoder flush at the end of a run (a partial enc-batch per lane) is then amortised as in
 a real video, instead of weighing on a 10-20 step sample.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5]
+  python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the result
+line.  --full adds every other leg (the detector's per-kernel solo / shared timings and the rooflines
+built on them, the sustained / host-frame / drift legs, the grouping legs of c5, the CPU baseline);
+--no-extras and --no-cpu-baseline trim a --full run.  --dump-outputs DIR writes what the timed region
+returned (dump_outputs) so that two builds can be compared output for output: the inputs are seeded
+and identical from run to run.
 With --gpus N > 1 and no torchrun environment the script starts
 `torch.distributed.run --nproc-per-node N` itself (before touching a GPU) and exits with its code;
 under torchrun WORLD_SIZE must equal --gpus.
@@ -110,8 +116,14 @@ def parse(argv=None):
                     help='frames per repeat of the CPU-baseline sample (default: BASELINE config 1\'s 64 for '
                          'MTCNN, 16 for YOLO; warm-up 1 frame, min of --cpu-repeats)')
     ap.add_argument('--cpu-repeats', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the solo / sustained / host-frame / drift legs')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, run every other leg too: detector kernel timings + rooflines, '
+                         'sustained / host-frame / drift legs, grouping (c5), CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the timed region\'s outputs as DIR/<name>.npy (see dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true',
+                    help='with --full: skip the sustained / host-frame / drift legs (two solo det-batches, not four)')
     # box post-processing (detection.py:174-262): the reference's defaults (main.py:18)
     ap.add_argument('--det-min-score', type=float, default=0.4)
     ap.add_argument('--det-min-size', type=int, default=50)
@@ -233,6 +245,32 @@ def measure(pipe, steps, warmup, ctx):
     faces, = ctx.reduce([sum(stats)], dist.ReduceOp.SUM)
     el, = ctx.reduce([elapsed], dist.ReduceOp.MAX)
     return faces, el, gathered, stats
+
+
+DUMP_ROW_BYTES = 32 << 20  # per dumped embedding array; dump_outputs stays far below 64 MB in all
+
+
+def dump_outputs(path, gathered, stats, max_bytes=DUMP_ROW_BYTES):
+    """What a caller of the timed region (measure -> pipe.run) received, as float arrays under
+    `path` (rank 0 writes; `stats` are this rank's faces per step, its rows come first in the
+    rank-ordered `gathered`):
+      embeddings_last_step.npy  float32 [n, D]  the last timed step's embeddings, in (frame, face) order
+      faces_per_step.npy        float64 [steps] faces each timed step produced
+      embeddings.npy            float32 [m, D]  rows of all gathered embeddings: every row, or, above
+                                                `max_bytes`, a fixed sample (seed 0, ascending rows)
+      embeddings_rows.npy       float64 [m]     the row numbers of embeddings.npy in the gathered array
+    Arrays above `max_bytes` are cut to their first rows (last step) or sampled (all rows)."""
+    os.makedirs(path, exist_ok=True)
+    X = gathered.detach().to(torch.float32).cpu().numpy()
+    cap = max(1, max_bytes // max(1, 4 * X.shape[1]))
+    n_local, n_last = int(sum(stats)), int(stats[-1]) if len(stats) else 0
+    np.save(os.path.join(path, 'embeddings_last_step.npy'), X[n_local - n_last:n_local][:cap])
+    np.save(os.path.join(path, 'faces_per_step.npy'), np.asarray(stats, dtype=np.float64))
+    rows = np.arange(X.shape[0])
+    if X.shape[0] > cap:
+        rows = np.sort(np.random.default_rng(0).choice(X.shape[0], cap, replace=False))
+    np.save(os.path.join(path, 'embeddings.npy'), X[rows])
+    np.save(os.path.join(path, 'embeddings_rows.npy'), rows.astype(np.float64))
 
 
 # ------------------------------------------------------------------ GPU pipelines
@@ -754,24 +792,14 @@ def grouping_leg(X, ctx, dev, rows_fn=None, grouper=None):
     return rec, mins, labels, scores
 
 
-def run_gpu(args):
-    ctx = Ctx('nccl')
+def full_legs(args, ctx, pipe, gathered, out):
+    """--full: everything the benchmark measures besides the headline region, after it.  Fills
+    `out` with the extra legs' records; returns (shared, solo, grouping): the detector kernel's
+    event timings with the lanes running together and with the chip to itself (None for the
+    encoder-only config), and config 5's grouping record."""
     dev = ctx.device
-    if args.det_model == 'none':
-        pipe = EncodePipeline(args, dev, ctx.rank)
-    else:
-        warm = max(args.warmup, max(1, args.lanes))
-        frames, offset, frames_np = rank_frames(args, ctx, warm + args.steps)
-        if args.touch:
-            # frames resident in HBM: one byte per 4 KB page read once (the page translations warm,
-            # as for a video pipeline's reused frame buffers; 1/4096 of the bytes, far below the
-            # 256 MB Infinity Cache's reach over the run's frames), outside the timed region
-            frames.view(-1)[::4096].sum()
-        pipe = DetEncPipeline(args, dev, frames, offset, frames_np)
-    ctx.sync()
-    faces, elapsed, gathered, _ = measure(pipe, args.steps, max(args.warmup, getattr(pipe, 'L', 1)), ctx)
     det = args.det_model != 'none'
-    shared = None
+    shared = solo = None
     if det:
         for d in pipe.dets:
             d.profile(True)
@@ -779,7 +807,6 @@ def run_gpu(args):
         shared = [0, 0, 0, 0]
         for d in pipe.dets:
             shared = [a + b for a, b in zip(shared, d.profile(False))]
-    out = {}
     extras = not args.no_extras
     if det and extras:
         solo = pipe.solo(4)
@@ -829,12 +856,39 @@ def run_gpu(args):
         rec = grouping_leg(torch.from_numpy(Xv).to(dev), ctx, dev)[0]
         rec['note'] = ('synth.video_embeddings(gathered rows, 30000, seed=5): ' + rec['note'])
         out['grouping_video'] = rec
+    return shared, solo, grouping
+
+
+def run_gpu(args):
+    ctx = Ctx('nccl')
+    dev = ctx.device
+    if args.det_model == 'none':
+        pipe = EncodePipeline(args, dev, ctx.rank)
+    else:
+        warm = max(args.warmup, max(1, args.lanes))
+        frames, offset, frames_np = rank_frames(args, ctx, warm + args.steps)
+        if args.touch:
+            # frames resident in HBM: one byte per 4 KB page read once (the page translations warm,
+            # as for a video pipeline's reused frame buffers; 1/4096 of the bytes, far below the
+            # 256 MB Infinity Cache's reach over the run's frames), outside the timed region
+            frames.view(-1)[::4096].sum()
+        pipe = DetEncPipeline(args, dev, frames, offset, frames_np)
+    ctx.sync()
+    faces, elapsed, gathered, stats = measure(pipe, args.steps, max(args.warmup, getattr(pipe, 'L', 1)), ctx)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, gathered, stats)
+    det = args.det_model != 'none'
+    out = {}
+    shared = solo = grouping = None
+    if args.full:
+        shared, solo, grouping = full_legs(args, ctx, pipe, gathered, out)
     if ctx.rank == 0:
         steps = args.steps
         frames_all = ctx.world * steps * (args.det_batch if det else 0)
         dtype_enc = args.enc_precision if args.enc_precision != 'f16x' else 'fp32 (split-fp16 MFMA)'
         if det:
-            roof, _ = roofline_det(args, pipe, shared, solo)
+            # (the detector's rooflines stand on the solo / shared kernel timings: --full only)
+            roof = roofline_det(args, pipe, shared, solo)[0] if args.full else None
             wl = ('YOLOv3(%s)' % args.det_precision if args.det_model == 'yolo'
                   else 'MTCNN(min_face_size=%g)' % args.min_face_size) + '+' + ENC_NAMES[args.enc_model]
             dtype = '%s det / %s enc' % (args.det_precision if args.det_model == 'yolo' else 'fp32 (split-fp16 MFMA)',
@@ -874,15 +928,17 @@ def run_gpu(args):
             'faces_per_frame': round(faces / max(1, frames_all), 3) if det else None,
             'frames_per_s': round(frames_all / elapsed, 2) if det else None,
             'embeddings_gathered': int(gathered.shape[0]),
+            'full': args.full,
             'roofline': roof,
-            'roofline_e2e': roofline_e2e(args, faces / max(1, ctx.world * steps), elapsed * 1e3 / steps,
-                                         solo if det else None, getattr(pipe, 'solo_stats', None)),
+            'roofline_e2e': (roofline_e2e(args, faces / max(1, ctx.world * steps), elapsed * 1e3 / steps,
+                                          solo if det else None, getattr(pipe, 'solo_stats', None))
+                             if args.full or not det else None),
             'cpu_baseline': None,
         }
         res.update(out)
         if grouping:
             res['grouping'] = grouping
-        if ctx.world == 1 and not args.no_cpu_baseline:
+        if args.full and ctx.world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(args, getattr(pipe, 'frames_np', None))
         print(json.dumps(res), flush=True)
     ctx.close()

@@ -34,6 +34,49 @@ def test_presets_and_overrides():
     assert (a.det_model, a.det_batch, a.enc_precision, a.det_min_size) == ('yolo', 8, 'fp32', 50)
 
 
+def test_plain_run_is_the_default():
+    """--full (every leg besides the headline region) and --dump-outputs are off unless asked for,
+    and --steps sets the timed steps whatever the config"""
+    import bench
+    a = bench.parse(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(['--config', 'c4', '--steps', '3', '--full', '--dump-outputs', 'd'])
+    assert (a.full, a.dump_outputs, a.steps) == (True, 'd', 3)
+
+
+def test_dump_outputs(tmp_path):
+    """dump_outputs writes what measure() returned: the last timed step's rows, the faces per
+    step and every gathered row (float32 / float64 .npy); above the byte cap a fixed sample of
+    the rows, the same on every call"""
+    import numpy as np
+    import bench
+    pipe = StubPipeline(0, 1)
+    ctx = bench.Ctx('gloo', device=torch.device('cpu'))
+    _, _, gathered, stats = bench.measure(pipe, pipe.steps(), 0, ctx)
+    last = torch.cat(pipe.run(pipe.steps() - 1, 1)[1])
+    assert last.shape[0] == stats[-1] > 0
+    d = str(tmp_path / 'a' / 'b')
+    bench.dump_outputs(d, gathered, stats)
+    got = {n: np.load(os.path.join(d, n + '.npy')) for n in
+           ('embeddings_last_step', 'faces_per_step', 'embeddings', 'embeddings_rows')}
+    assert sorted(os.listdir(d)) == sorted(n + '.npy' for n in got)
+    assert [got[n].dtype for n in got] == [np.float32, np.float64, np.float32, np.float64]
+    assert np.array_equal(got['embeddings_last_step'], last.numpy())
+    assert got['faces_per_step'].tolist() == stats
+    assert np.array_equal(got['embeddings'], gathered.numpy())
+    assert got['embeddings_rows'].tolist() == list(range(gathered.shape[0]))
+    # a cap of 10 rows (2 float32 columns): 10 sampled rows in ascending order, twice the same
+    d2, d3 = str(tmp_path / 'c'), str(tmp_path / 'd')
+    bench.dump_outputs(d2, gathered, stats, max_bytes=80)
+    bench.dump_outputs(d3, gathered, stats, max_bytes=80)
+    rows = np.load(os.path.join(d2, 'embeddings_rows.npy'))
+    assert rows.shape == (10,) and np.all(np.diff(rows) > 0) and rows[-1] < gathered.shape[0]
+    assert np.array_equal(np.load(os.path.join(d2, 'embeddings.npy')), gathered.numpy()[rows.astype(int)])
+    for n in got:
+        assert np.array_equal(np.load(os.path.join(d2, n + '.npy')), np.load(os.path.join(d3, n + '.npy')))
+    assert np.load(os.path.join(d2, 'embeddings_last_step.npy')).shape[0] == min(10, stats[-1])
+
+
 def test_spawn_command():
     import bench
     cmd = bench.spawn_command(8, ['--gpus', '8', '--steps', '5'], 29511)
