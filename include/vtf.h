@@ -225,6 +225,19 @@ int vtf_ahash_crops(const uint8_t* d_frames, int F, int H, int W, int64_t frame_
  * d_arg int64 [N]. */
 int vtf_hamming_dedupe(const uint64_t* d_hashes, int64_t N, int32_t* d_min, int64_t* d_arg, void* hip_stream);
 
+/* ---------------------------------------------------------------- face files
+ * cv2.imwrite(path, crop) of detection.py:155-158 on device: baseline JFIF, 4:2:0, libjpeg's
+ * bytes.  frames / crops (host int32 [N,5], validated) as in vtf_ahash_crops.  quality 1..100.
+ * d_out: device bytes, file i at [out_offsets[i], out_offsets[i+1]); out_offsets host int64
+ * [N+1].  If the files need more than cap bytes nothing is written, *out_total says how many,
+ * VTF_E_CAPACITY.  Returns after the stream is synchronised (the offsets are host values).
+ * VTF_E_ARG: a null pointer, quality outside 1..100, an empty rectangle or one outside the frame,
+ * a bad frame index.  N = 0 is fine (out_offsets[0] = 0).  Scratch: the stream's arena
+ * (vtf_release_stream). */
+int vtf_jpeg_encode_crops(const uint8_t* d_frames, int F, int H, int W, int64_t frame_stride, int64_t row_stride,
+                          const int32_t* crops, int64_t N, int quality, uint8_t* d_out, int64_t cap,
+                          int64_t* out_offsets, int64_t* out_total, void* hip_stream);
+
 /* ---------------------------------------------------------------- video frames
  * The decode side of process_video (src/videotofaces/detection.py:68-111, which hands the
  * detector cv2.VideoCapture / decord BGR frames [B,H,W,3]): planar YUV frames in HBM (as a

@@ -6,12 +6,19 @@
   grouping  the grouping step on N planted-cluster embeddings (N=10k, D=512 by default):
             fused cosine dedupe (dupes.py:51-68) and the KMeans + silhouette/CH/DB sweep
             (grouping.py:92-137) for k = 2..16, each timed with a device sync on both sides.
+  jpeg      the face-file write of one det-batch (detection.py:155-158): 16 device-generated 720p
+            frames, the crops detect_crops gives for them (MTCNN; a fixed list of 48 rectangles of
+            100-250 px when that yields fewer than 16), quality 95.  Two legs in one process:
+            host = one .cpu().numpy() slice per crop + utils.imwrite (the jpeg_encoder='host'
+            path), device = utils.jpeg_encode_crops + writing the same files.  ms per det-batch,
+            the ratio and the bytes each moves D2H.
 
 The CPU legs are the oracle (ViT torch-CPU restatement) and sklearn 1.7.2 itself (the
 reference's own grouping dependency), on bounded samples, timed on this host's cores.
 
   python scripts/bench_stages.py vit [--vit-model vit_l] [--steps 10] [--warmup 2]
   python scripts/bench_stages.py grouping [--n 10000] [--d 512]
+  python scripts/bench_stages.py jpeg [--steps 20] [--warmup 3]
 """
 import argparse
 import json
@@ -145,9 +152,87 @@ def bench_grouping(a):
     print(json.dumps(res), flush=True)
 
 
+def bench_jpeg(a):
+    import tempfile
+    from videotofaces import synth
+    from videotofaces.detection import detect_crops
+    from videotofaces.detectors.mtcnn import RealMTCNN
+    from videotofaces.utils import imwrite, jpeg_encode_crops
+    dev = torch.device('cuda:0')
+    B, H, W = 16, 720, 1280
+    frames = synth.make_frames_device(0, B, H, W, seed=0, device=dev, style='blobs')
+    import contextlib
+    with contextlib.redirect_stdout(sys.stderr):  # (the model announces itself; stdout is the JSON line)
+        model = RealMTCNN(dev)
+    with torch.inference_mode():
+        d_crops, _ = detect_crops(model, frames, 0)
+    rects = d_crops.cpu().numpy()
+    source = 'detect_crops (MTCNN, default box settings)'
+    if len(rects) < 16:
+        rng = np.random.default_rng(0)
+        rects = []
+        for i in range(48):
+            w, h = int(rng.integers(100, 251)), int(rng.integers(100, 251))
+            x, y = int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1))
+            rects.append([i % B, x, y, x + w, y + h])
+        rects = np.array(rects, np.int32)
+        source = 'fixed list (seeded): 48 rectangles of 100-250 px'
+    n = len(rects)
+    names = ['%06d.jpg' % i for i in range(n)]
+
+    def host_leg(d):
+        for (fi, x1, y1, x2, y2), fn in zip(rects.tolist(), names):
+            imwrite(os.path.join(d, fn), np.ascontiguousarray(frames[fi][y1:y2, x1:x2].cpu().numpy()))
+
+    def device_leg(d):
+        for data, fn in zip(jpeg_encode_crops(frames, rects, 95), names):
+            with open(os.path.join(d, fn), 'wb') as f:
+                f.write(data)
+
+    def encode_only(d):
+        jpeg_encode_crops(frames, rects, 95)
+
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for leg, fn in (('host', host_leg), ('device', device_leg), ('device_encode_only', encode_only)):
+            d = os.path.join(tmp, leg)
+            os.makedirs(d)
+            for _ in range(a.warmup):
+                fn(d)
+            torch.cuda.synchronize(dev)
+            ts = []
+            for _ in range(a.steps):
+                t0 = time.perf_counter()
+                fn(d)
+                torch.cuda.synchronize(dev)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            out[leg] = ts
+        sizes = {leg: sum(os.path.getsize(os.path.join(tmp, leg, f)) for f in names) for leg in ('host', 'device')}
+    try:
+        import cv2  # noqa: F401
+        writer = 'cv2.imwrite'
+    except ImportError:
+        writer = 'Pillow save(quality=95)'
+    pix = int(((rects[:, 3] - rects[:, 1]).astype(np.int64) * (rects[:, 4] - rects[:, 2])).sum())
+    med = {k: float(np.median(v)) for k, v in out.items()}
+    res = {'metric': 'face JPEG write, ms per det-batch (16 x 720p frames, %d crops, quality 95)' % n,
+           'value': round(med['device'], 3), 'unit': 'ms', 'higher_is_better': False, 'n_gpus': 1,
+           'steps': a.steps, 'warmup': a.warmup, 'data': 'synthetic (device-generated blobs frames, seed 0)',
+           'config': {'crops': n, 'crop_source': source, 'crop_pixels': pix, 'host_writer': writer,
+                      'host_cores_used': 1},
+           'host_ms': round(med['host'], 3), 'host_ms_min': round(min(out['host']), 3),
+           'device_ms': round(med['device'], 3), 'device_ms_min': round(min(out['device']), 3),
+           'device_encode_only_ms': round(med['device_encode_only'], 3),
+           'host_over_device': round(med['host'] / med['device'], 2),
+           'd2h_bytes': {'host': pix * 3, 'device': sizes['device']},
+           'd2h_copies': {'host': n, 'device': 1},
+           'file_bytes': sizes, 'files_identical_size': sizes['host'] == sizes['device']}
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('stage', choices=['vit', 'grouping'])
+    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg'])
     ap.add_argument('--vit-model', default='vit_l', choices=['vit_b', 'vit_l'])
     ap.add_argument('--vit-precision', default='f16x', choices=['fp32', 'f16x'])
     ap.add_argument('--enc-batch', type=int, default=128)
@@ -160,7 +245,7 @@ def main():
     ap.add_argument('--cpu-ks', type=int, default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
-    bench_vit(a) if a.stage == 'vit' else bench_grouping(a)
+    {'vit': bench_vit, 'grouping': bench_grouping, 'jpeg': bench_jpeg}[a.stage](a)
 
 
 if __name__ == '__main__':

@@ -180,16 +180,21 @@ class _HostFrame:
         return self.t[key].cpu().numpy()
 
 
-def process_frames_batch(frames, indices, model, det_params, save_params, hash_thr, hashes):
+def process_frames_batch(frames, indices, model, det_params, save_params, hash_thr, hashes, jpeg_encoder='host'):
     """detection.py:126-158 with the frames uploaded to HBM once: detect and filter/adjust the
     boxes on device (detect_crops), average hashes of the crops on device, nearest-5 hash
-    dedupe, JPEG save.  Returns (file names, updated `hashes` list)."""
+    dedupe, JPEG save.  Returns (file names, updated `hashes` list).
+    jpeg_encoder='device': the crops that survive the dedupe are encoded on the GPU in one call
+    (utils.jpeg_encode_crops) and the files are written from the returned bytes; no crop's pixels
+    come to the host.  With resize_to set the host path is used: resizing stays on the host."""
     import os.path as osp
     import numpy as np
     import torch
     from .dupes import ahash_crops, ahash, nearest_dupes
     from .utils import resize_keep_ratio, imwrite
     from . import _native as nat
+    if jpeg_encoder not in ('host', 'device'):
+        raise ValueError("jpeg_encoder must be 'host' or 'device'")
     _, mscore, msize, mborder, scale, square = det_params
     out_dir, out_prefix, resize_to, _, _, _ = save_params
     if isinstance(frames, torch.Tensor):  # frames already in HBM (a .y4m source; strided views are fine)
@@ -202,6 +207,8 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     with torch.inference_mode():
         d_crops, _ = detect_crops(model, fr_dev, 0, mscore, msize, mborder, scale, square)
     rects = d_crops.cpu().numpy()
+    if jpeg_encoder == 'device' and not resize_to:
+        return _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes), hashes
     faces, seen = [], {}
     for fi, x1, y1, x2, y2 in rects.tolist():
         j = seen.get(fi, 0)
@@ -221,9 +228,32 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     return [fn for _, fn in faces], hashes
 
 
-def detect_faces(files, model, vid_params, det_params, save_params, hash_thr):
+def _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes):
+    """The hash dedupe and JPEG save of process_frames_batch with the encoder on the device:
+    file names and rectangles only on the host, one D2H of the compressed bytes."""
+    import os.path as osp
+    from .dupes import ahash_crops, nearest_dupes
+    from .utils import jpeg_encode_crops
+    names, seen = [], {}
+    for fi in rects[:, 0].tolist():
+        j = seen.get(fi, 0)
+        seen[fi] = j + 1
+        names.append(out_prefix + '%06d_%u.jpg' % (indices[fi], j))
+    keep = list(range(len(names)))
+    if hash_thr and hash_thr != -1 and names:
+        flags, _ = nearest_dupes(list(zip(ahash_crops(fr_dev, rects), names)), hashes, hash_thr)
+        keep = [i for i, d in zip(keep, flags) if not d]
+    names = [names[i] for i in keep]
+    for fn, data in zip(names, jpeg_encode_crops(fr_dev, rects[keep], 95)):
+        with open(osp.join(out_dir, 'faces', fn), 'wb') as f:
+            f.write(data)
+    return names
+
+
+def detect_faces(files, model, vid_params, det_params, save_params, hash_thr, jpeg_encoder='host'):
     """detection.py:32-65: every video in det-batches of sampled frames, then the overall hash
-    dedupe.  Saving annotated frames / rejects (debug IO) is not mirrored."""
+    dedupe.  Saving annotated frames / rejects (debug IO) is not mirrored.  jpeg_encoder: see
+    process_frames_batch."""
     import os
     import os.path as osp
     import numpy as np
@@ -251,7 +281,7 @@ def detect_faces(files, model, vid_params, det_params, save_params, hash_thr):
             if video_area:
                 cx1, cy1, cx2, cy2 = video_area
                 frames = frames[:, cy1:cy2, cx1:cx2, :]
-            fn_b, hashes = process_frames_batch(frames, bi, model, det_params, sp, hash_thr, hashes)
+            fn_b, hashes = process_frames_batch(frames, bi, model, det_params, sp, hash_thr, hashes, jpeg_encoder)
             fnames.extend(fn_b)
         hashes_all.extend(h for (h, _) in hashes)  # the kept faces' hashes (detection.py:123)
     if hash_thr and hash_thr != -1 and fnames:

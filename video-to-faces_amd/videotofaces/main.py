@@ -12,7 +12,12 @@ and every all-pairs / K-means pass runs in libvtf_hip.so.  Additions, all opt-in
     'fp32' (default, fp32 MFMA: the parity mode), 'bf16' (bf16 operands; FaceNet, YOLO, R-CNN)
     or 'f16x' (fp32 operands split into two fp16 parts, fp32-grade products; ViT).  The
     reference-default paths (det_model / enc_model 'default') keep the reference classes'
-    defaults.
+    defaults;
+  * jpeg_encoder='device' encodes the face JPEGs of a det-batch on the GPU
+    (vtf_jpeg_encode_crops: libjpeg's baseline 4:2:0 bytes at quality 95) and brings only the
+    compressed bytes to the host in one copy; 'host' (default) slices every crop to the host and
+    writes it with OpenCV / Pillow as the reference does.  With resize_to set, 'device' uses
+    the host path for that call: resizing stays on the host.
 """
 import os.path as osp
 
@@ -59,12 +64,14 @@ def video_to_faces(input_path=None, input_ext=None,
                    ref_dir=None, random_state=0, group_log=True,
                    enc_dup_thr=0.25, enc_oth_thr=0.9,
                    _test_enc=False, _test_exclude_other=False,
-                   decoupled=False, det_precision='fp32', enc_precision='fp32'):
+                   decoupled=False, det_precision='fp32', enc_precision='fp32', jpeg_encoder='host'):
     from .detection import detect_faces
     from .dupes import remove_dupes_overall
     from .grouping import encode_faces, cluster_faces, classify_faces
     if not prep.validate_args(mode, input_path, out_dir, style, group_mode, video_reader, det_model, enc_model,
                               decoupled):
+        return
+    if not prep._one_of(jpeg_encoder, 'jpeg_encoder', ['host', 'device']):
         return
     if _test_enc:
         raise NotImplementedError('_test_enc needs a labels.txt ground truth (grouping.py:140-155)')
@@ -101,7 +108,8 @@ def video_to_faces(input_path=None, input_ext=None,
         det_params = (det_batch_size, det_min_score, det_min_size, det_min_border, det_scale, det_square)
         save_params = (out_dir, out_prefix, resize_to, save_frames, save_rejects, save_dupes)
         detector = get_detector(style, det_model, device, det_precision)
-        imgpaths = detect_faces(files, detector, vid_params, det_params, save_params, hash_thr)
+        imgpaths = detect_faces(files, detector, vid_params, det_params, save_params, hash_thr,
+                                jpeg_encoder=jpeg_encoder)
     if mode in ('full', 'grouping') and imgpaths:
         encoder = get_encoder(style, enc_model, device, enc_precision)
         features = encode_faces(imgpaths, encoder, enc_batch_size, enc_area)

@@ -64,3 +64,44 @@ def imwrite(path, img):
         from PIL import Image
         Image.fromarray(img[:, :, ::-1]).save(path, quality=95)
         return True
+
+
+def jpeg_encode_crops(frames_dev, crops, quality=95):
+    """cv2.imwrite of every crop (int [N,5] frame, x1, y1, x2, y2) of the CUDA uint8 BGR frames
+    [B,H,W,3] on the device (vtf_jpeg_encode_crops) -> list of N `bytes`, each a whole baseline
+    JPEG file with the bytes libjpeg writes at `quality` (what Pillow's save(quality=) gives for
+    the crop's RGB pixels).  One library call (a second one with the exact size when the first
+    guess of the output capacity was too small) and one D2H copy of the bytes used."""
+    import ctypes
+    import numpy as np
+    import torch
+    from . import _native as nat
+    if not (isinstance(frames_dev, torch.Tensor) and frames_dev.is_cuda and frames_dev.dtype == torch.uint8
+            and frames_dev.dim() == 4 and frames_dev.shape[3] == 3):
+        raise ValueError('frames must be a CUDA uint8 tensor [B,H,W,3]')
+    crops = np.ascontiguousarray(np.asarray(crops, np.int32).reshape(-1, 5))
+    n = crops.shape[0]
+    if n == 0:
+        return []
+    if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
+        frames_dev = frames_dev.contiguous()
+    B, H, W = frames_dev.shape[:3]
+    dev = frames_dev.device
+    offs = np.zeros(n + 1, np.int64)
+    total = ctypes.c_int64(0)
+    # first guess: the header and a byte per pixel (quality 95 photographs need about half that)
+    w, h = (crops[:, 3] - crops[:, 1]).astype(np.int64), (crops[:, 4] - crops[:, 2]).astype(np.int64)
+    cap = int((1024 + np.maximum(w, 0) * np.maximum(h, 0)).sum())
+    with torch.cuda.device(dev):
+        for attempt in (0, 1):
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            rc = nat.lib().vtf_jpeg_encode_crops(nat.ptr(frames_dev), B, H, W, frames_dev.stride(0),
+                                                 frames_dev.stride(1), crops.ctypes.data, n, int(quality),
+                                                 nat.ptr(out), cap, offs.ctypes.data, ctypes.byref(total),
+                                                 nat.stream_ptr(dev))
+            if rc != nat.VTF_E_CAPACITY or attempt:
+                break
+            cap = int(total.value)
+    nat.check(rc)
+    data = out[:int(offs[n])].cpu().numpy().tobytes()
+    return [data[offs[i]:offs[i + 1]] for i in range(n)]
