@@ -238,6 +238,40 @@ int vtf_jpeg_encode_crops(const uint8_t* d_frames, int F, int H, int W, int64_t 
                           const int32_t* crops, int64_t N, int quality, uint8_t* d_out, int64_t cap,
                           int64_t* out_offsets, int64_t* out_total, void* hip_stream);
 
+/* cv2.imread(path) of grouping.py:29-40 on device: baseline 4:2:0 face files -> libjpeg's pixels.
+ * A file is decoded on the device if it is SOF0, 8-bit, three components sampled 2x2 / 1x1 / 1x1,
+ * one interleaved scan (Ss 0, Se 63, Ah = Al = 0), 8-bit DQT, any DHT tables, no restart interval,
+ * no Adobe APP14 segment, EXIF orientation absent or 1 (what cv2.imwrite, Pillow's defaults and
+ * vtf_jpeg_encode_crops write).  Everything else is classified on the host and reaches no kernel.
+ *
+ * vtf_jpeg_probe: host only, no GPU: parses one file's headers.  Never reads outside
+ * [data, data + len).  info[8]:
+ *   [0] h, [1] w (0 when no frame header was read)
+ *   [2] kind: 0 = decodable on the device, 1 = a JPEG with whole headers but unsupported,
+ *             2 = not a JPEG, or the headers end before the scan starts
+ *   [3] scan_begin, [4] scan_end: the entropy-coded bytes [begin, end) relative to data; the scan
+ *       ends at the first 0xFF that is not followed by 0x00, or at len (kind 0 and 1 only)
+ *   [5] why (kind 1): bits 1 not SOF0, 2 sample / DQT precision, 4 not three YCbCr components, 8 sampling,
+ *       16 restart interval, 32 Adobe segment, 64 EXIF orientation, 128 scan parameters or more than
+ *       EOI after the scan, 256 missing or malformed table, 512 size
+ *   [6] number of components, [7] 0 */
+int vtf_jpeg_probe(const uint8_t* data, int64_t len, int32_t* info);
+/* N files, host bytes back to back (file i at [offsets[i], offsets[i+1])), decoded into N slots of
+ * a device uint8 BGR buffer [N][Hmax][Wmax][3] at the given strides (bytes).  One H2D copy of the
+ * bytes.  A file writes only rows < h and columns < w of its slot.  out_sizes host int32 [N,2] =
+ * (h, w); out_status host int32 [N]: 0 ok, 1 unsupported, 2 corrupt (or not a JPEG), 3 larger than
+ * Hmax x Wmax (slot untouched for 1 and 3, its Hmax x Wmax pixels zero-filled for 2).  A per-file
+ * problem is reported in out_status, not as the return code.  VTF_E_ARG: null pointers, N < 0,
+ * decreasing offsets, strides too small.  N = 0 is fine.  Returns after the stream is
+ * synchronised.  Scratch: the stream's arena (vtf_release_stream). */
+int vtf_jpeg_decode(const uint8_t* data, const int64_t* offsets, int64_t N, uint8_t* d_bgr, int Hmax, int Wmax,
+                    int64_t frame_stride, int64_t row_stride, int32_t* out_sizes, int32_t* out_status,
+                    void* hip_stream);
+/* Stage timing of vtf_jpeg_decode on the calling thread: enable != 0 makes later calls bracket
+ * their kernels with HIP events; out_ms (may be null) receives the last timed call's
+ * (entropy decode, IDCT + upsampling + colour) milliseconds. */
+int vtf_jpeg_decode_profile(int enable, float* out_ms);
+
 /* ---------------------------------------------------------------- video frames
  * The decode side of process_video (src/videotofaces/detection.py:68-111, which hands the
  * detector cv2.VideoCapture / decord BGR frames [B,H,W,3]): planar YUV frames in HBM (as a

@@ -12,6 +12,13 @@
             host = one .cpu().numpy() slice per crop + utils.imwrite (the jpeg_encoder='host'
             path), device = utils.jpeg_encode_crops + writing the same files.  ms per det-batch,
             the ratio and the bytes each moves D2H.
+  jpeg_decode  the face-file read of the grouping stage (grouping.py:29-40): about 1,024 face files
+            written by the device encoder from device-generated 720p frames and the crops
+            detect_crops gives for them.  Two legs in one process: host = encode_faces' path up to
+            the uploaded buffer (_imread of every file, pad into [n,Hmax,Wmax,3], one H2D copy per
+            enc-batch of 16), device = reading the bytes + utils.jpeg_decode in groups of
+            grouping.DECODE_GROUP files.  ms per 1,024 files (scaled when fewer files), the ratio,
+            the bytes each moves H2D and the two kernel stages by HIP events.
 
 The CPU legs are the oracle (ViT torch-CPU restatement) and sklearn 1.7.2 itself (the
 reference's own grouping dependency), on bounded samples, timed on this host's cores.
@@ -19,6 +26,7 @@ reference's own grouping dependency), on bounded samples, timed on this host's c
   python scripts/bench_stages.py vit [--vit-model vit_l] [--steps 10] [--warmup 2]
   python scripts/bench_stages.py grouping [--n 10000] [--d 512]
   python scripts/bench_stages.py jpeg [--steps 20] [--warmup 3]
+  python scripts/bench_stages.py jpeg_decode [--steps 10] [--warmup 3]
 """
 import argparse
 import json
@@ -230,9 +238,122 @@ def bench_jpeg(a):
     print(json.dumps(res), flush=True)
 
 
+def bench_jpeg_decode(a):
+    import contextlib
+    import tempfile
+    from videotofaces import _native as nat
+    from videotofaces import grouping, synth
+    from videotofaces.detection import detect_crops
+    from videotofaces.detectors.mtcnn import RealMTCNN
+    from videotofaces.utils import jpeg_decode, jpeg_encode_crops
+    dev = torch.device('cuda:0')
+    B, H, W, want, bs = 16, 720, 1280, 1024, 16
+    with contextlib.redirect_stdout(sys.stderr):
+        model = RealMTCNN(dev)
+    files, source = [], 'detect_crops (MTCNN, default box settings)'
+    rng = np.random.default_rng(0)
+    for seed in range(64):
+        frames = synth.make_frames_device(0, B, H, W, seed=seed, device=dev, style='blobs')
+        with torch.inference_mode():
+            d_crops, _ = detect_crops(model, frames, 0)
+        rects = d_crops.cpu().numpy()
+        if len(rects) < 16:
+            rects = []
+            for i in range(48):
+                w, h = int(rng.integers(100, 251)), int(rng.integers(100, 251))
+                x, y = int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1))
+                rects.append([i % B, x, y, x + w, y + h])
+            rects = np.array(rects, np.int32)
+            source = 'fixed list (seeded): rectangles of 100-250 px'
+        files += jpeg_encode_crops(frames, rects, 95)
+        if len(files) >= want:
+            break
+    files = files[:want]
+    n = len(files)
+    del frames
+    group = grouping.DECODE_GROUP
+
+    def host_leg(paths):
+        moved = 0
+        for at in range(0, n, bs):
+            images = [grouping._imread(p) for p in paths[at:at + bs]]
+            hm, wm = max(im.shape[0] for im in images), max(im.shape[1] for im in images)
+            buf = np.zeros((len(images), hm, wm, 3), np.uint8)
+            for i, im in enumerate(images):
+                buf[i, :im.shape[0], :im.shape[1]] = im
+            torch.from_numpy(buf).to(dev)
+            moved += buf.nbytes
+        return moved
+
+    stage_ms = np.zeros(2, np.float32)
+
+    def device_leg(paths):
+        moved, st = 0, np.zeros(2)
+        for at in range(0, n, group):
+            data = []
+            for p in paths[at:at + group]:
+                with open(p, 'rb') as f:
+                    data.append(f.read())
+            atlas, sizes, status = jpeg_decode(data, dev)
+            assert not status.any()
+            moved += sum(len(d) for d in data)
+            nat.check(nat.lib().vtf_jpeg_decode_profile(1, stage_ms.ctypes.data))
+            st += stage_ms
+        device_leg.stages.append(st)
+        return moved
+    device_leg.stages = []
+
+    out, moved = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = [os.path.join(tmp, '%06d.jpg' % i) for i in range(n)]
+        for p, data in zip(paths, files):
+            with open(p, 'wb') as f:
+                f.write(data)
+        # the two paths give the same pixels
+        atlas, sizes, status = jpeg_decode(files[:64], dev)
+        got = atlas.cpu().numpy()
+        for i in range(64):
+            im = grouping._imread(paths[i])
+            assert status[i] == 0 and np.array_equal(got[i, :im.shape[0], :im.shape[1]], im), i
+        nat.check(nat.lib().vtf_jpeg_decode_profile(1, None))
+        for leg, fn in (('host', host_leg), ('device', device_leg)):
+            for _ in range(a.warmup):
+                fn(paths)
+            torch.cuda.synchronize(dev)
+            device_leg.stages = []
+            ts = []
+            for _ in range(a.steps):
+                t0 = time.perf_counter()
+                moved[leg] = fn(paths)
+                torch.cuda.synchronize(dev)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            out[leg] = ts
+        nat.check(nat.lib().vtf_jpeg_decode_profile(0, None))
+    try:
+        import cv2  # noqa: F401
+        reader = 'cv2.imread'
+    except ImportError:
+        reader = 'Pillow open().convert(RGB)'
+    scale = 1024.0 / n
+    med = {k: float(np.median(v)) * scale for k, v in out.items()}
+    stages = np.median(np.array(device_leg.stages), axis=0) * scale
+    res = {'metric': 'face JPEG read for grouping, ms per 1024 files (quality 95, crops of 720p frames)',
+           'value': round(med['device'], 3), 'unit': 'ms', 'higher_is_better': False, 'n_gpus': 1,
+           'steps': a.steps, 'warmup': a.warmup, 'data': 'synthetic (device-generated blobs frames, device-encoded)',
+           'config': {'files': n, 'crop_source': source, 'file_bytes': sum(len(f) for f in files),
+                      'host_reader': reader, 'host_cores_used': 1, 'host_enc_batch': bs, 'device_group': group},
+           'host_ms': round(med['host'], 3), 'host_ms_min': round(min(out['host']) * scale, 3),
+           'device_ms': round(med['device'], 3), 'device_ms_min': round(min(out['device']) * scale, 3),
+           'device_stage1_entropy_ms': round(float(stages[0]), 3),
+           'device_stage2_pixels_ms': round(float(stages[1]), 3),
+           'host_over_device': round(med['host'] / med['device'], 2),
+           'h2d_bytes': moved, 'h2d_copies': {'host': -(-n // bs), 'device': -(-n // group)}}
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg'])
+    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg', 'jpeg_decode'])
     ap.add_argument('--vit-model', default='vit_l', choices=['vit_b', 'vit_l'])
     ap.add_argument('--vit-precision', default='f16x', choices=['fp32', 'f16x'])
     ap.add_argument('--enc-batch', type=int, default=128)
@@ -245,7 +366,7 @@ def main():
     ap.add_argument('--cpu-ks', type=int, default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
-    {'vit': bench_vit, 'grouping': bench_grouping, 'jpeg': bench_jpeg}[a.stage](a)
+    {'vit': bench_vit, 'grouping': bench_grouping, 'jpeg': bench_jpeg, 'jpeg_decode': bench_jpeg_decode}[a.stage](a)
 
 
 if __name__ == '__main__':

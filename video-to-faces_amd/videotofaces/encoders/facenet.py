@@ -93,11 +93,25 @@ def blob_from_images(images, size, mean, scale, device):
         h, w = im.shape[:2]
         buf[i, :h, :w] = im
         crops[i] = (i, 0, 0, w, h)
-    fr = torch.from_numpy(buf).to(device)
+    return blob_from_frames(torch.from_numpy(buf).to(device), crops, size, mean, scale)
+
+
+def blob_from_frames(frames_dev, crops, size, mean, scale):
+    """The blob kernel of blob_from_images on frames already in HBM: CUDA uint8 BGR [F,H,W,3] and
+    host int crops [N,5] (frame, x1, y1, x2, y2) -> fp32 [N,3,size,size]."""
+    device = frames_dev.device
+    crops = np.ascontiguousarray(crops, np.int32).reshape(-1, 5)
+    n = crops.shape[0]
+    out = torch.empty((n, 3, size, size), dtype=torch.float32, device=device)
+    if n == 0:
+        return out
+    if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
+        frames_dev = frames_dev.contiguous()
+    F, H, W = frames_dev.shape[:3]
     dc = torch.from_numpy(crops).to(device)
-    nat.check(nat.lib().vtf_blob_from_crops(nat.ptr(fr), n, Hm, Wm, fr.stride(0), fr.stride(1), nat.ptr(dc), n, size,
-                                            ctypes.c_float(mean), ctypes.c_float(scale), nat.ptr(out),
-                                            nat.stream_ptr(device)))
+    nat.check(nat.lib().vtf_blob_from_crops(nat.ptr(frames_dev), F, H, W, frames_dev.stride(0), frames_dev.stride(1),
+                                            nat.ptr(dc), n, size, ctypes.c_float(mean), ctypes.c_float(scale),
+                                            nat.ptr(out), nat.stream_ptr(device)))
     return out
 
 
@@ -118,6 +132,15 @@ class FaceNet():
 
     def __call__(self, images):
         inp = blob_from_images(images, 160, 127.5, 1 / 128, self.model.device)
+        return self.encode_blob(inp)
+
+    def blob_from_frames(self, frames_dev, crops):
+        """__call__'s blob step on device frames: CUDA uint8 BGR [F,H,W,3] + host int crops [N,5]
+        (frame, x1, y1, x2, y2) -> the encoder's input [N,3,160,160] on the device."""
+        return blob_from_frames(frames_dev, crops, 160, 127.5, 1 / 128)
+
+    def encode_blob(self, inp):
+        """__call__'s forward: blob [N,3,160,160] -> np.ndarray f32 [N,512]."""
         with torch.inference_mode():
             out = self.model(inp)
         return out.cpu().numpy()

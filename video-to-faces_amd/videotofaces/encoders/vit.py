@@ -14,7 +14,7 @@ import torch
 
 from .. import _native as nat
 from .. import synth
-from .facenet import blob_from_images
+from .facenet import blob_from_frames, blob_from_images
 
 
 class ViT:
@@ -100,6 +100,15 @@ class AnimeVIT():
 
     def __call__(self, images):
         inp = blob_from_images(images, 128, 127.5, 1 / 127.5, self.model.device)
+        return self.encode_blob(inp)
+
+    def blob_from_frames(self, frames_dev, crops):
+        """__call__'s blob step on device frames: CUDA uint8 BGR [F,H,W,3] + host int crops [N,5]
+        (frame, x1, y1, x2, y2) -> the encoder's input [N,3,128,128] on the device."""
+        return blob_from_frames(frames_dev, crops, 128, 127.5, 1 / 127.5)
+
+    def encode_blob(self, inp):
+        """__call__'s forward: blob [N,3,128,128] -> np.ndarray f32 [N,768|1024]."""
         with torch.inference_mode():
             out = self.model(inp)
         return out.cpu().numpy()

@@ -40,10 +40,109 @@ def _imread(p):
         return np.asarray(Image.open(p).convert('RGB'))[:, :, ::-1].copy()
 
 
-def encode_faces(paths, model, bs, area):
-    """grouping.py:29-40: batches of images -> model -> concatenated [N, D]."""
+# jpeg_decoder='device': files per vtf_jpeg_decode call, the atlas bytes one call may take and the
+# longest side a file may have in a shared atlas (a larger one is decoded on the host and makes a
+# group of its own, so it does not enlarge the slots of other files)
+DECODE_GROUP = 512
+DECODE_ATLAS_BYTES = 1 << 30
+DECODE_MAX_SIDE = 1024
+
+
+def _area_rect(h, w, area):
+    """crop_to_area's slice of an h x w image as (x1, y1, x2, y2), clipped as numpy clips it."""
+    if not area:
+        return 0, 0, w, h
+    px1, py1, px2, py2 = area
+    x1, x2, _ = slice(int(px1 * w), int(px2 * w + 1)).indices(w)
+    y1, y2, _ = slice(int(py1 * h), int(py2 * h + 1)).indices(h)
+    return x1, y1, max(x1, x2), max(y1, y2)
+
+
+def _decode_group(paths, at):
+    """The next group of files from paths[at:] -> (files, probed, host, hm, wm): the files' bytes,
+    their probed (h, w, kind), the images already read on the host {index: BGR array} (files the
+    device does not decode, and oversize ones) and the atlas size.  A group ends at DECODE_GROUP
+    files or before the file that would take the atlas past DECODE_ATLAS_BYTES; a file with a side
+    above DECODE_MAX_SIDE is a group of its own.  Never empty."""
+    from .utils import jpeg_probe
+    files, probed, host, hm, wm = [], [], {}, 1, 1
+    while at + len(files) < len(paths) and len(files) < DECODE_GROUP:
+        i = len(files)
+        with open(paths[at + i], 'rb') as f:
+            data = f.read()
+        h, w, kind = jpeg_probe(data)
+        img = None
+        if kind != 0 or max(h, w) > DECODE_MAX_SIDE:
+            img = _imread(paths[at + i])  # (fails here as it fails on the host path)
+            h, w = img.shape[:2]
+        big = max(h, w) > DECODE_MAX_SIDE
+        if files and (big or (i + 1) * max(hm, h) * max(wm, w) * 3 > DECODE_ATLAS_BYTES):
+            break  # this file starts the next group (nothing of it is kept here)
+        if img is not None:
+            host[i] = img
+        files.append(data)
+        probed.append((h, w, kind))
+        hm, wm = max(hm, h), max(wm, w)
+        if big:
+            break
+    return files, probed, host, hm, wm
+
+
+def _encode_faces_device(paths, model, bs, area):
+    """encode_faces with the files decoded on the GPU (utils.jpeg_decode).  The files are decoded in
+    groups (_decode_group), whatever `bs` is; every group's blobs come from the blob kernel
+    model(images) runs, and the forward runs on the same batches of `bs` blobs in the same order, so
+    the embeddings are the host path's bits.  A file the device does not decode (progressive,
+    grayscale, corrupt, ...) or one with a side above DECODE_MAX_SIDE is read with _imread as on the
+    host path and copied into its slot of the group's one atlas."""
+    from .utils import jpeg_decode
+    dev = nat.device_of(model)
+    x, pending = [], None  # blobs that wait for a full batch
+
+    def flush(blobs, last):
+        nonlocal pending
+        pending = blobs if pending is None else torch.cat([pending, blobs])
+        while pending.shape[0] >= bs or (last and pending.shape[0]):
+            x.append(model.encode_blob(pending[:bs]))
+            pending = pending[bs:]
+
+    at = 0
+    while at < len(paths):
+        files, probed, host, hm, wm = _decode_group(paths, at)
+        if len(files) == 1 and host:  # one host-decoded file (an oversize one): its pixels are the atlas
+            atlas = torch.from_numpy(np.ascontiguousarray(host[0])[None]).to(dev)
+            sizes, status, host = np.array([host[0].shape[:2]], np.int32), np.zeros(1, np.int32), {}
+        else:
+            atlas, sizes, status = jpeg_decode(files, dev, probed=probed, min_size=(hm, wm))
+        for i in np.flatnonzero(status != 0):
+            if int(i) not in host:  # the scan turned out to be damaged
+                host[int(i)] = _imread(paths[at + int(i)])
+        for i, img in host.items():
+            h, w = img.shape[:2]
+            if h > atlas.shape[1] or w > atlas.shape[2]:  # (a reader that disagrees with the frame header)
+                grown = torch.zeros((len(files), max(h, atlas.shape[1]), max(w, atlas.shape[2]), 3),
+                                    dtype=torch.uint8, device=dev)
+                grown[:, :atlas.shape[1], :atlas.shape[2]] = atlas
+                atlas = grown
+            atlas[i, :h, :w] = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+            sizes[i] = (h, w)
+        crops = np.array([(i,) + _area_rect(int(sizes[i, 0]), int(sizes[i, 1]), area) for i in range(len(files))],
+                         np.int32).reshape(-1, 5)
+        at += len(files)
+        flush(model.blob_from_frames(atlas, crops), at >= len(paths))
+    return np.concatenate(x)
+
+
+def encode_faces(paths, model, bs, area, jpeg_decoder='host'):
+    """grouping.py:29-40: batches of images -> model -> concatenated [N, D].  jpeg_decoder='device'
+    (an addition) decodes the files on the GPU instead of one by one on the host: the same pixels,
+    the same blob kernel and forward, the same embeddings."""
     from .utils import crop_to_area
+    if jpeg_decoder not in ('host', 'device'):
+        raise ValueError("jpeg_decoder must be 'host' or 'device'")
     print('Extracting features from images for grouping')
+    if jpeg_decoder == 'device' and len(paths):
+        return _encode_faces_device(paths, model, bs, area)
     x = []
     for bn in range(math.ceil(len(paths) / bs)):
         images = [_imread(p) for p in paths[bs * bn:bs * (bn + 1)]]

@@ -17,7 +17,12 @@ and every all-pairs / K-means pass runs in libvtf_hip.so.  Additions, all opt-in
     (vtf_jpeg_encode_crops: libjpeg's baseline 4:2:0 bytes at quality 95) and brings only the
     compressed bytes to the host in one copy; 'host' (default) slices every crop to the host and
     writes it with OpenCV / Pillow as the reference does.  With resize_to set, 'device' uses
-    the host path for that call: resizing stays on the host.
+    the host path for that call: resizing stays on the host;
+  * jpeg_decoder='device' decodes the face files for grouping on the GPU (vtf_jpeg_decode:
+    libjpeg's pixels for baseline 4:2:0 files, a few hundred files per call, only the compressed
+    bytes uploaded); 'host' (default) reads them one by one with OpenCV / Pillow as the reference
+    does.  A file the device does not decode (progressive, grayscale, corrupt, ...) is read on the
+    host as before; the embeddings are the same bits either way.  Reference images stay on the host.
 """
 import os.path as osp
 
@@ -64,7 +69,8 @@ def video_to_faces(input_path=None, input_ext=None,
                    ref_dir=None, random_state=0, group_log=True,
                    enc_dup_thr=0.25, enc_oth_thr=0.9,
                    _test_enc=False, _test_exclude_other=False,
-                   decoupled=False, det_precision='fp32', enc_precision='fp32', jpeg_encoder='host'):
+                   decoupled=False, det_precision='fp32', enc_precision='fp32', jpeg_encoder='host',
+                   jpeg_decoder='host'):
     from .detection import detect_faces
     from .dupes import remove_dupes_overall
     from .grouping import encode_faces, cluster_faces, classify_faces
@@ -72,6 +78,8 @@ def video_to_faces(input_path=None, input_ext=None,
                               decoupled):
         return
     if not prep._one_of(jpeg_encoder, 'jpeg_encoder', ['host', 'device']):
+        return
+    if not prep._one_of(jpeg_decoder, 'jpeg_decoder', ['host', 'device']):
         return
     if _test_enc:
         raise NotImplementedError('_test_enc needs a labels.txt ground truth (grouping.py:140-155)')
@@ -112,7 +120,7 @@ def video_to_faces(input_path=None, input_ext=None,
                                 jpeg_encoder=jpeg_encoder)
     if mode in ('full', 'grouping') and imgpaths:
         encoder = get_encoder(style, enc_model, device, enc_precision)
-        features = encode_faces(imgpaths, encoder, enc_batch_size, enc_area)
+        features = encode_faces(imgpaths, encoder, enc_batch_size, enc_area, jpeg_decoder=jpeg_decoder)
         if enc_dup_thr and enc_dup_thr != -1:
             features, imgpaths = remove_dupes_overall(features, imgpaths, ('enc', enc_dup_thr, save_dupes, out_dir),
                                                       device=device)

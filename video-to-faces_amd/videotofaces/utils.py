@@ -105,3 +105,50 @@ def jpeg_encode_crops(frames_dev, crops, quality=95):
     nat.check(rc)
     data = out[:int(offs[n])].cpu().numpy().tobytes()
     return [data[offs[i]:offs[i + 1]] for i in range(n)]
+
+
+def jpeg_probe(data):
+    """Headers of one JPEG file (`bytes`) parsed on the host (vtf_jpeg_probe, no GPU) ->
+    (h, w, kind): kind 0 = decodable on the device (baseline 4:2:0), 1 = another JPEG,
+    2 = not a JPEG or truncated headers."""
+    import numpy as np
+    from . import _native as nat
+    info = np.zeros(8, np.int32)
+    buf = np.frombuffer(data, np.uint8)
+    nat.check(nat.lib().vtf_jpeg_probe(buf.ctypes.data if len(buf) else None, len(buf), info.ctypes.data))
+    return int(info[0]), int(info[1]), int(info[2])
+
+
+def jpeg_decode(files, device=None, probed=None, min_size=(1, 1)):
+    """cv2.imread of every file (a list of `bytes`, each a whole JPEG file) on the device
+    (vtf_jpeg_decode) -> (atlas, sizes, status): a CUDA uint8 BGR tensor [N,Hmax,Wmax,3] with file
+    i in atlas[i, :h, :w] (the rest of a slot is not written), np.int32 [N,2] (h, w) and np.int32
+    [N]: 0 decoded, 1 a JPEG the device does not decode (anything but baseline 4:2:0; slot
+    untouched), 2 corrupt or no JPEG (slot zeroed), 3 too large (never here: the atlas is sized
+    from the probed headers).  The pixels are libjpeg's, bit for bit.  The headers are probed on
+    the host to size the atlas; then one library call and one H2D copy of the compressed bytes.
+    probed: jpeg_probe's (h, w, kind) of every file when the caller has them already.  min_size:
+    (Hmax, Wmax) is at least this, for slots the caller fills itself (files with status != 0)."""
+    import numpy as np
+    import torch
+    from . import _native as nat
+    dev = nat.require_gpu(device)
+    n = len(files)
+    sizes, status = np.zeros((n, 2), np.int32), np.zeros(n, np.int32)
+    if probed is None:
+        probed = [jpeg_probe(f) for f in files]
+    hm, wm = max(1, int(min_size[0])), max(1, int(min_size[1]))
+    for h, w, kind in probed:
+        if kind == 0:
+            hm, wm = max(hm, h), max(wm, w)
+    atlas = torch.empty((n, hm, wm, 3), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return atlas, sizes, status
+    offs = np.zeros(n + 1, np.int64)
+    np.cumsum([len(f) for f in files], out=offs[1:])
+    data = np.frombuffer(b''.join(files) or b'\0', np.uint8)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().vtf_jpeg_decode(data.ctypes.data, offs.ctypes.data, n, nat.ptr(atlas), hm, wm,
+                                            atlas.stride(0), atlas.stride(1), sizes.ctypes.data, status.ctypes.data,
+                                            nat.stream_ptr(dev)))
+    return atlas, sizes, status
