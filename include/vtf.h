@@ -237,6 +237,18 @@ int vtf_hamming_dedupe(const uint64_t* d_hashes, int64_t N, int32_t* d_min, int6
 int vtf_jpeg_encode_crops(const uint8_t* d_frames, int F, int H, int W, int64_t frame_stride, int64_t row_stride,
                           const int32_t* crops, int64_t N, int quality, uint8_t* d_out, int64_t cap,
                           int64_t* out_offsets, int64_t* out_total, void* hip_stream);
+/* vtf_jpeg_encode_crops (the same files, offsets and errors) that also leaves, for every crop, the
+ * BGR pixels libjpeg decodes from the crop's file: reconstructed on the device from the quantised
+ * coefficients the encoder holds, so no file is entropy-decoded for them.  d_pixels: device bytes,
+ * crop i as tight [h][w][3] rows at byte offset sum over j < i of h_j * w_j * 3 (any alignment);
+ * pixels_cap below that sum over all crops: VTF_E_ARG.  out_status host int32 [N]: 0, or 2 for a
+ * crop whose reconstruction left the int16 range (never for coefficients of 8-bit pixels); its
+ * pixels are then unspecified.  With VTF_E_CAPACITY d_pixels is not written either.  The same
+ * number of host syncs as vtf_jpeg_encode_crops. */
+int vtf_jpeg_encode_crops_decoded(const uint8_t* d_frames, int F, int H, int W, int64_t frame_stride,
+                                  int64_t row_stride, const int32_t* crops, int64_t N, int quality, uint8_t* d_out,
+                                  int64_t cap, int64_t* out_offsets, int64_t* out_total, uint8_t* d_pixels,
+                                  int64_t pixels_cap, int32_t* out_status, void* hip_stream);
 
 /* cv2.imread(path) of grouping.py:29-40 on device: baseline 4:2:0 face files -> libjpeg's pixels.
  * A file is decoded on the device if it is SOF0, 8-bit, three components sampled 2x2 / 1x1 / 1x1,
@@ -267,6 +279,15 @@ int vtf_jpeg_probe(const uint8_t* data, int64_t len, int32_t* info);
 int vtf_jpeg_decode(const uint8_t* data, const int64_t* offsets, int64_t N, uint8_t* d_bgr, int Hmax, int Wmax,
                     int64_t frame_stride, int64_t row_stride, int32_t* out_sizes, int32_t* out_status,
                     void* hip_stream);
+/* Faces that are in HBM already into the slots of such a buffer: faces host array [N] of device
+ * pointers to tight [h][w][3] pixels (vtf_jpeg_encode_crops_decoded's), sizes host int32 [N,2] =
+ * (h, w); face i is copied to rows < h and columns < w of slot i of d_atlas [N][Hmax][Wmax][3] at
+ * the given strides (bytes), nothing else is written.  A null entry of faces leaves its slot alone
+ * (the caller fills it; its size is not looked at).  One launch.  VTF_E_ARG: null arguments, N < 0,
+ * h > Hmax, w > Wmax, strides too small (vtf_jpeg_decode's rule).  N = 0 is fine.  Returns after
+ * the stream is synchronised.  Scratch: the stream's arena (vtf_release_stream). */
+int vtf_faces_to_atlas(const uint8_t* const* faces, const int32_t* sizes, int64_t N, uint8_t* d_atlas, int Hmax,
+                       int Wmax, int64_t frame_stride, int64_t row_stride, void* hip_stream);
 /* Stage timing of vtf_jpeg_decode on the calling thread: enable != 0 makes later calls bracket
  * their kernels with HIP events; out_ms (may be null) receives the last timed call's
  * (entropy decode, IDCT + upsampling + colour) milliseconds. */

@@ -19,6 +19,13 @@
             enc-batch of 16), device = reading the bytes + utils.jpeg_decode in groups of
             grouping.DECODE_GROUP files.  ms per 1,024 files (scaled when fewer files), the ratio,
             the bytes each moves H2D and the two kernel stages by HIP events.
+  handoff   the face hand-off from detection to grouping (face_handoff='device'): jpeg_decode's
+            inputs, encoded with decoded=True so that a FaceStore holds every face's decoded pixels
+            in HBM.  Three legs in one process, each up to the atlas in HBM: host = jpeg_decode's
+            host leg, device = reading the bytes + utils.jpeg_decode, store = utils.faces_to_atlas
+            from the store, in groups of grouping.DECODE_GROUP (no file opened).  ms per 1,024
+            faces and the ratios; also the encode call of one det-batch with decoded=False and
+            decoded=True (the surcharge the detection stage pays for the stored pixels).
 
 The CPU legs are the oracle (ViT torch-CPU restatement) and sklearn 1.7.2 itself (the
 reference's own grouping dependency), on bounded samples, timed on this host's cores.
@@ -27,6 +34,7 @@ reference's own grouping dependency), on bounded samples, timed on this host's c
   python scripts/bench_stages.py grouping [--n 10000] [--d 512]
   python scripts/bench_stages.py jpeg [--steps 20] [--warmup 3]
   python scripts/bench_stages.py jpeg_decode [--steps 10] [--warmup 3]
+  python scripts/bench_stages.py handoff [--steps 10] [--warmup 3]
 """
 import argparse
 import json
@@ -351,9 +359,156 @@ def bench_jpeg_decode(a):
     print(json.dumps(res), flush=True)
 
 
+def bench_handoff(a):
+    import contextlib
+    import tempfile
+    from videotofaces import grouping, synth
+    from videotofaces.detection import detect_crops
+    from videotofaces.detectors.mtcnn import RealMTCNN
+    from videotofaces.facestore import FaceStore
+    from videotofaces.utils import faces_to_atlas, jpeg_decode, jpeg_encode_crops
+    dev = torch.device('cuda:0')
+    B, H, W, want, bs = 16, 720, 1280, 1024, 16
+    with contextlib.redirect_stdout(sys.stderr):
+        model = RealMTCNN(dev)
+    # jpeg_decode's inputs, encoded with decoded=True: the files and, per det-batch, a chunk of pixels
+    files, chunks, source = [], [], 'detect_crops (MTCNN, default box settings)'
+    rng = np.random.default_rng(0)
+    first = None
+    for seed in range(64):
+        frames = synth.make_frames_device(0, B, H, W, seed=seed, device=dev, style='blobs')
+        with torch.inference_mode():
+            d_crops, _ = detect_crops(model, frames, 0)
+        rects = d_crops.cpu().numpy()
+        if len(rects) < 16:
+            rects = []
+            for i in range(48):
+                w, h = int(rng.integers(100, 251)), int(rng.integers(100, 251))
+                x, y = int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1))
+                rects.append([i % B, x, y, x + w, y + h])
+            rects = np.array(rects, np.int32)
+            source = 'fixed list (seeded): rectangles of 100-250 px'
+        if first is None:
+            first = (frames, rects)
+        fs, pixels, offsets, status = jpeg_encode_crops(frames, rects, 95, decoded=True)
+        assert not status.any()
+        chunks.append((len(files), pixels, offsets, np.stack([rects[:, 4] - rects[:, 2], rects[:, 3] - rects[:, 1]], 1)))
+        files += fs
+        if len(files) >= want:
+            break
+    files = files[:want]
+    n = len(files)
+    del frames
+    group = grouping.DECODE_GROUP
+
+    # the encode call of one det-batch, without and with the decoded pixels
+    # (a call is a fraction of a millisecond: the two take turns, so that neither has the warmer clocks,
+    # and ten times the steps of the legs)
+    enc = {False: [], True: []}
+    for step in range(-a.warmup, 10 * a.steps):
+        for decoded in (False, True):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            jpeg_encode_crops(first[0], first[1], 95, decoded=decoded)
+            torch.cuda.synchronize(dev)
+            if step >= 0:
+                enc[decoded].append((time.perf_counter() - t0) * 1e3)
+
+    def host_leg(paths, store):
+        moved = 0
+        for at in range(0, n, bs):
+            images = [grouping._imread(p) for p in paths[at:at + bs]]
+            hm, wm = max(im.shape[0] for im in images), max(im.shape[1] for im in images)
+            buf = np.zeros((len(images), hm, wm, 3), np.uint8)
+            for i, im in enumerate(images):
+                buf[i, :im.shape[0], :im.shape[1]] = im
+            torch.from_numpy(buf).to(dev)
+            moved += buf.nbytes
+        return moved
+
+    def device_leg(paths, store):
+        moved = 0
+        for at in range(0, n, group):
+            data = []
+            for p in paths[at:at + group]:
+                with open(p, 'rb') as f:
+                    data.append(f.read())
+            atlas, sizes, status = jpeg_decode(data, dev)
+            assert not status.any()
+            moved += sum(len(d) for d in data)
+        return moved
+
+    def store_atlas(paths, store, at):
+        ents = [store.get(p) for p in paths[at:at + group]]
+        sizes = np.array([(h, w) for _, _, h, w in ents], np.int32)
+        faces = [c[o:o + h * w * 3] for c, o, h, w in ents]
+        return faces_to_atlas(faces, sizes, int(sizes[:, 0].max()), int(sizes[:, 1].max()), dev), sizes
+
+    def store_leg(paths, store):
+        for at in range(0, n, group):
+            store_atlas(paths, store, at)
+        return 0
+
+    out, moved = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = [os.path.join(tmp, '%06d.jpg' % i) for i in range(n)]
+        for p, data in zip(paths, files):
+            with open(p, 'wb') as f:
+                f.write(data)
+        store = FaceStore()
+        for at, pixels, offsets, sizes in chunks:
+            k = max(0, min(len(sizes), n - at))
+            assert store.add(paths[at:at + k], pixels, offsets[:k], sizes[:k])
+        assert len(store) == n
+        # the store path gives the decoder's pixels
+        atlas, sizes = store_atlas(paths, store, 0)
+        ref, rsz, status = jpeg_decode(files[:group], dev)
+        assert not status.any() and np.array_equal(sizes, rsz)
+        for i in range(len(sizes)):
+            h, w = sizes[i]
+            assert torch.equal(atlas[i, :h, :w], ref[i, :h, :w]), i
+        del atlas, ref
+        for leg, fn in (('host', host_leg), ('device', device_leg), ('store', store_leg)):
+            for _ in range(a.warmup):
+                fn(paths, store)
+            torch.cuda.synchronize(dev)
+            ts = []
+            for _ in range(a.steps):
+                t0 = time.perf_counter()
+                moved[leg] = fn(paths, store)
+                torch.cuda.synchronize(dev)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            out[leg] = ts
+        store_bytes = store.nbytes
+    try:
+        import cv2  # noqa: F401
+        reader = 'cv2.imread'
+    except ImportError:
+        reader = 'Pillow open().convert(RGB)'
+    scale = 1024.0 / n
+    med = {k: float(np.median(v)) * scale for k, v in out.items()}
+    e0, e1 = float(np.median(enc[False])), float(np.median(enc[True]))
+    res = {'metric': 'face hand-off to grouping, ms per 1024 faces (quality 95, crops of 720p frames)',
+           'value': round(med['store'], 3), 'unit': 'ms', 'higher_is_better': False, 'n_gpus': 1,
+           'steps': a.steps, 'warmup': a.warmup, 'data': 'synthetic (device-generated blobs frames, device-encoded)',
+           'config': {'faces': n, 'crop_source': source, 'file_bytes': sum(len(f) for f in files),
+                      'store_bytes': store_bytes, 'chunks': len(chunks), 'host_reader': reader, 'host_cores_used': 1,
+                      'host_enc_batch': bs, 'device_group': group},
+           'host_ms': round(med['host'], 3), 'host_ms_min': round(min(out['host']) * scale, 3),
+           'device_ms': round(med['device'], 3), 'device_ms_min': round(min(out['device']) * scale, 3),
+           'store_ms': round(med['store'], 3), 'store_ms_min': round(min(out['store']) * scale, 3),
+           'device_over_store': round(med['device'] / med['store'], 2),
+           'host_over_store': round(med['host'] / med['store'], 2),
+           'h2d_bytes': moved,
+           'encode_call': {'crops': int(len(first[1])), 'steps': len(enc[True]), 'order': 'alternating', 'plain_ms': round(e0, 3), 'plain_ms_min': round(min(enc[False]), 3),
+                           'decoded_ms': round(e1, 3), 'decoded_ms_min': round(min(enc[True]), 3),
+                           'surcharge_ms': round(e1 - e0, 3), 'decoded_over_plain': round(e1 / e0, 3)}}
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg', 'jpeg_decode'])
+    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg', 'jpeg_decode', 'handoff'])
     ap.add_argument('--vit-model', default='vit_l', choices=['vit_b', 'vit_l'])
     ap.add_argument('--vit-precision', default='f16x', choices=['fp32', 'f16x'])
     ap.add_argument('--enc-batch', type=int, default=128)
@@ -366,7 +521,8 @@ def main():
     ap.add_argument('--cpu-ks', type=int, default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
-    {'vit': bench_vit, 'grouping': bench_grouping, 'jpeg': bench_jpeg, 'jpeg_decode': bench_jpeg_decode}[a.stage](a)
+    {'vit': bench_vit, 'grouping': bench_grouping, 'jpeg': bench_jpeg, 'jpeg_decode': bench_jpeg_decode,
+     'handoff': bench_handoff}[a.stage](a)
 
 
 if __name__ == '__main__':

@@ -27,11 +27,18 @@
 //                 per crop) and the EOI marker.
 // Three host syncs per call: the word buffer's size, the file sizes (capacity check, offsets),
 // the end.
+//
+// vtf_jpeg_encode_crops_decoded is the same call (encode_crops below) with two more launches
+// before the last sync: k_jpeg_idct and k_jpeg_pixels of jpeg_recon.hpp, the decoder's own
+// reconstruction stage, turn k_jpeg_mcu's coefficient buffer (exactly what a decoder's Huffman
+// stage would rebuild from the file) into the pixels libjpeg decodes from each file, tightly
+// packed in HBM for the grouping stage.
 #include <cstring>
 #include <vector>
 
 #include "boxes.hpp"
 #include "common.hpp"
+#include "jpeg_recon.hpp"
 #include "nms.hpp"
 
 namespace vtf {
@@ -91,6 +98,7 @@ struct JpegTables {
     uint32_t dc[2][12];    // Huffman code | length << 16, by symbol
     uint32_t ac[2][256];
     uint8_t header[JPEG_HEADER + 1];
+    uint16_t quant[3][64];  // the plain quantisers of Y, Cb, Cr, zigzag: what a decoder multiplies by (jpeg_recon.hpp)
 };
 constexpr int SOF_HEIGHT_AT = 2 + 18 + 2 * 69 + 5;  // height, width (big endian u16) inside SOF0
 
@@ -112,6 +120,8 @@ void build_tables(int quality, JpegTables& t) {
             const int v = std::min(255, std::max(1, (Q_BASE[c][k] * s + 50) / 100));
             q[c][k] = (uint8_t)v;
             t.qdiv[c][k] = (uint16_t)(8 * v);
+            t.quant[c][k] = (uint16_t)v;
+            if (c) t.quant[2][k] = (uint16_t)v;
         }
     uint8_t dcv[12];
     for (int i = 0; i < 12; i++) dcv[i] = (uint8_t)i;
@@ -198,17 +208,9 @@ __device__ inline void fdct8(int* d, int s) {
     d[s] = descale(t7 + z1 + z4, N);
 }
 
-// index of the crop that owns element i of a partition given by its ascending bounds[0..N]
-__device__ inline int owner(const int32_t* __restrict__ bounds, int N, int i) {
-    int lo = 0, hi = N;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (bounds[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+// (owner(bounds, N, i): the crop that owns element i of a partition, jpeg_recon.hpp)
 
-constexpr int ROW = 9;            // LDS row stride of a block (8 + 1: rows and columns conflict-free)
+constexpr int ROW = 9;           // LDS row stride of a block (8 + 1: rows and columns conflict-free)
 constexpr int BLK = 8 * ROW;
 
 // mcu0[c]: first MCU of crop c (ascending, mcu0[N] = all MCUs)
@@ -493,6 +495,132 @@ __global__ __launch_bounds__(64) void k_jpeg_header(const JpegTables* __restrict
     }
 }
 
+// Both entry points.  decoded: also reconstruct every crop from its coefficients (jpeg_recon.hpp)
+// into d_pixels, tightly packed in crop order, and report the per-crop status.  The two
+// reconstruction launches go last, behind the capacity check (a call that fails it writes
+// nothing), and end with the call's last sync.
+void encode_crops(const uint8_t* d_frames, int F, int H, int W, int64_t frame_stride, int64_t row_stride,
+                  const int32_t* crops, int64_t N, int quality, uint8_t* d_out, int64_t cap, int64_t* out_offsets,
+                  int64_t* out_total, bool decoded, uint8_t* d_pixels, int64_t pixels_cap, int32_t* out_status,
+                  hipStream_t st) {
+    VTF_CHECK(out_offsets && out_total, VTF_E_ARG, "null argument");
+    VTF_CHECK(N >= 0 && F > 0 && H > 0 && W > 0 && cap >= 0, VTF_E_ARG, "bad argument");
+    VTF_CHECK(quality >= 1 && quality <= 100, VTF_E_ARG, "jpeg quality must be 1..100");
+    VTF_CHECK(H <= 65535 && W <= 65535, VTF_E_ARG, "a JPEG is at most 65535 pixels wide or high");
+    VTF_CHECK(!decoded || pixels_cap >= 0, VTF_E_ARG, "bad argument");
+    out_offsets[0] = 0;
+    *out_total = 0;
+    if (N == 0) return;
+    VTF_CHECK(d_frames && crops && (d_out || cap == 0), VTF_E_ARG, "null argument");
+    VTF_CHECK(N < (1 << 24), VTF_E_LIMIT, "jpeg: too many crops in one call");
+    check_crops_host(crops, N, F, H, W);
+    if (decoded) {
+        VTF_CHECK(d_pixels && out_status, VTF_E_ARG, "null argument");
+        int64_t need = 0;
+        for (int64_t i = 0; i < N; i++) {
+            const int32_t* c = crops + i * 5;
+            need += (int64_t)(c[3] - c[1]) * (c[4] - c[2]) * 3;
+        }
+        VTF_CHECK(pixels_cap >= need, VTF_E_ARG, "jpeg: pixels_cap is below the crops' h * w * 3 bytes");
+    }
+    StreamScratch sc = stream_scratch(st);
+    Arena& ar = *sc.ar;
+
+    // host tables: crops, first MCU of every crop, (decoded: where every crop's pixels go,) quality
+    // tables -> one pinned block, one copy
+    const size_t crops_b = (size_t)N * 20, mcu0_b = ((size_t)N + 1) * 4;
+    const size_t recon_at = (crops_b + mcu0_b + 15) & ~(size_t)15;
+    const size_t tab_at = recon_at + (decoded ? (size_t)N * sizeof(ReconImage) : 0);
+    const size_t up_b = tab_at + sizeof(JpegTables);
+    Arena::Mail up = ar.mail(0, up_b);
+    int32_t* h_crops = (int32_t*)up.h;
+    int32_t* h_mcu0 = h_crops + N * 5;
+    ReconImage* h_recon = (ReconImage*)((uint8_t*)up.h + recon_at);
+    std::memcpy(h_crops, crops, crops_b);
+    int64_t mcus = 0, pixel_at = 0;
+    for (int64_t i = 0; i < N; i++) {
+        const int32_t* c = crops + i * 5;
+        const int w = c[3] - c[1], h = c[4] - c[2];
+        h_mcu0[i] = (int32_t)mcus;
+        mcus += (int64_t)((w + 15) >> 4) * ((h + 15) >> 4);
+        VTF_CHECK(mcus <= MAX_MCUS, VTF_E_LIMIT, "jpeg: too many pixels in one call");
+        if (decoded) {  // the call's one quantiser set; tight rows
+            h_recon[i] = ReconImage{h, w, (w + 15) >> 4, 0, pixel_at, (int64_t)w * 3};
+            pixel_at += (int64_t)h * w * 3;
+        }
+    }
+    h_mcu0[N] = (int32_t)mcus;
+    build_tables(quality, *(JpegTables*)((uint8_t*)up.h + tab_at));
+    uint8_t* d_up = (uint8_t*)ar.get(0, up_b);
+    VTF_HIP(hipMemcpyAsync(d_up, up.h, up_b, hipMemcpyHostToDevice, st));
+    const int32_t* d_crops = (const int32_t*)d_up;
+    const int32_t* d_mcu0 = d_crops + N * 5;
+    const ReconImage* d_recon = (const ReconImage*)(d_up + recon_at);
+    const JpegTables* d_tab = (const JpegTables*)(d_up + tab_at);
+
+    const int nblk = (int)(mcus * 6);
+    int16_t* coef = ar.get<int16_t>(1, (size_t)nblk * 64);
+    int32_t* mcu_crop = ar.get<int32_t>(2, (size_t)mcus);
+    int32_t* blk_bits = ar.get<int32_t>(3, (size_t)nblk);
+    int32_t* scan = ar.get<int32_t>(4, (size_t)nblk);
+    int32_t* lay = ar.get<int32_t>(5, 3 * (size_t)N + 1);  // bit0 [N], nbits [N], chunk0 [N + 1]
+    int32_t *bit0 = lay, *nbits = lay + N, *chunk0 = lay + 2 * N;
+    // results for the host: [0] chunks, then (bytes, 0xFF bytes) per crop
+    Arena::Mail res = ar.mail(1, (2 * (size_t)N + 1) * 4);
+    int32_t* h_res = (int32_t*)res.h;
+    int32_t* d_res = (int32_t*)res.d;
+
+    k_jpeg_mcu<<<(unsigned)mcus, 64, 0, st>>>(d_frames, frame_stride, row_stride, d_crops, d_mcu0, (int)N, d_tab, coef,
+                                              mcu_crop);
+    k_jpeg_bits<<<cdiv(nblk, 4), 256, 0, st>>>(coef, mcu_crop, d_mcu0, d_tab, nblk, blk_bits);
+    VTF_HIP(hipGetLastError());
+    inclusive_scan_i32(ar, 6, blk_bits, scan, nblk, st);
+    k_jpeg_layout<<<cdiv(N + 1, 256), 256, 0, st>>>(scan, d_mcu0, (int)N, bit0, nbits, chunk0, d_res);
+    VTF_HIP(hipGetLastError());
+    VTF_HIP(hipStreamSynchronize(st));
+    const int nchunks = h_res[0];
+
+    uint32_t* words = ar.get<uint32_t>(7, (size_t)nchunks * CHUNK_WORDS + 2);  // (+2: a lane's window)
+    int32_t* chunk_ff = ar.get<int32_t>(8, (size_t)nchunks);
+    int32_t* ffscan = ar.get<int32_t>(9, (size_t)nchunks);
+    VTF_HIP(hipMemsetAsync(words, 0, ((size_t)nchunks * CHUNK_WORDS + 2) * 4, st));
+    k_jpeg_pack<<<cdiv(nblk, 4), 256, 0, st>>>(coef, mcu_crop, d_mcu0, d_tab, nblk, scan, bit0, nbits, chunk0, words);
+    k_jpeg_ffs<<<cdiv(nchunks, 4), 256, 0, st>>>(words, chunk0, nbits, (int)N, nchunks, chunk_ff);
+    VTF_HIP(hipGetLastError());
+    inclusive_scan_i32(ar, 6, chunk_ff, ffscan, nchunks, st);
+    k_jpeg_sizes<<<cdiv(N, 256), 256, 0, st>>>(ffscan, chunk0, nbits, (int)N, d_res + 1);
+    VTF_HIP(hipGetLastError());
+    VTF_HIP(hipStreamSynchronize(st));
+
+    int64_t total = 0;
+    for (int64_t i = 0; i < N; i++) {
+        total += JPEG_HEADER + (int64_t)h_res[1 + 2 * i] + h_res[2 + 2 * i] + 2;
+        out_offsets[i + 1] = total;
+    }
+    *out_total = total;
+    VTF_CHECK(total <= cap, VTF_E_CAPACITY, "jpeg output capacity too small (*out_total bytes needed)");
+    Arena::Mail off = ar.mail(2, ((size_t)N + 1) * 8);
+    std::memcpy(off.h, out_offsets, ((size_t)N + 1) * 8);
+    int64_t* d_off = ar.get<int64_t>(10, (size_t)N + 1);
+    VTF_HIP(hipMemcpyAsync(d_off, off.h, ((size_t)N + 1) * 8, hipMemcpyHostToDevice, st));
+    k_jpeg_stuff<<<cdiv(nchunks, 4), 256, 0, st>>>(words, chunk0, nbits, ffscan, d_off, (int)N, nchunks, d_out);
+    k_jpeg_header<<<(unsigned)N, 64, 0, st>>>(d_tab, d_crops, d_off, d_out);
+    VTF_HIP(hipGetLastError());
+    Arena::Mail stat{nullptr, nullptr};
+    if (decoded) {
+        uint8_t* yplane = ar.get<uint8_t>(11, (size_t)mcus * 256);
+        uint8_t* cplane = ar.get<uint8_t>(12, (size_t)mcus * 128);
+        int32_t* d_status = ar.get<int32_t>(13, (size_t)N);
+        stat = ar.mail(3, (size_t)N * 4);
+        VTF_HIP(hipMemsetAsync(d_status, 0, (size_t)N * 4, st));
+        launch_recon(d_recon, d_mcu0, (int)N, mcus, &d_tab->quant[0][0], coef, d_status, yplane, cplane, d_pixels, st);
+        VTF_HIP(hipGetLastError());
+        VTF_HIP(hipMemcpyAsync(stat.h, d_status, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    }
+    VTF_HIP(hipStreamSynchronize(st));
+    if (decoded) std::memcpy(out_status, stat.h, (size_t)N * 4);
+}
+
 }  // namespace
 
 }  // namespace vtf
@@ -504,92 +632,18 @@ extern "C" int vtf_jpeg_encode_crops(const uint8_t* d_frames, int F, int H, int 
                                      uint8_t* d_out, int64_t cap, int64_t* out_offsets, int64_t* out_total,
                                      void* hip_stream) {
     return guarded_on(stream_device((hipStream_t)hip_stream), [&] {
-        VTF_CHECK(out_offsets && out_total, VTF_E_ARG, "null argument");
-        VTF_CHECK(N >= 0 && F > 0 && H > 0 && W > 0 && cap >= 0, VTF_E_ARG, "bad argument");
-        VTF_CHECK(quality >= 1 && quality <= 100, VTF_E_ARG, "jpeg quality must be 1..100");
-        VTF_CHECK(H <= 65535 && W <= 65535, VTF_E_ARG, "a JPEG is at most 65535 pixels wide or high");
-        out_offsets[0] = 0;
-        *out_total = 0;
-        if (N == 0) return;
-        VTF_CHECK(d_frames && crops && (d_out || cap == 0), VTF_E_ARG, "null argument");
-        VTF_CHECK(N < (1 << 24), VTF_E_LIMIT, "jpeg: too many crops in one call");
-        check_crops_host(crops, N, F, H, W);
-        hipStream_t st = (hipStream_t)hip_stream;
-        StreamScratch sc = stream_scratch(st);
-        Arena& ar = *sc.ar;
+        encode_crops(d_frames, F, H, W, frame_stride, row_stride, crops, N, quality, d_out, cap, out_offsets, out_total,
+                     false, nullptr, 0, nullptr, (hipStream_t)hip_stream);
+    });
+}
 
-        // host tables: crops, first MCU of every crop, quality tables -> one pinned block, one copy
-        const size_t crops_b = (size_t)N * 20, mcu0_b = ((size_t)N + 1) * 4;
-        const size_t up_b = ((crops_b + mcu0_b + 15) & ~(size_t)15) + sizeof(JpegTables);
-        Arena::Mail up = ar.mail(0, up_b);
-        int32_t* h_crops = (int32_t*)up.h;
-        int32_t* h_mcu0 = h_crops + N * 5;
-        std::memcpy(h_crops, crops, crops_b);
-        int64_t mcus = 0;
-        for (int64_t i = 0; i < N; i++) {
-            const int32_t* c = crops + i * 5;
-            h_mcu0[i] = (int32_t)mcus;
-            mcus += (int64_t)((c[3] - c[1] + 15) >> 4) * ((c[4] - c[2] + 15) >> 4);
-            VTF_CHECK(mcus <= MAX_MCUS, VTF_E_LIMIT, "jpeg: too many pixels in one call");
-        }
-        h_mcu0[N] = (int32_t)mcus;
-        const size_t tab_at = up_b - sizeof(JpegTables);
-        build_tables(quality, *(JpegTables*)((uint8_t*)up.h + tab_at));
-        uint8_t* d_up = (uint8_t*)ar.get(0, up_b);
-        VTF_HIP(hipMemcpyAsync(d_up, up.h, up_b, hipMemcpyHostToDevice, st));
-        const int32_t* d_crops = (const int32_t*)d_up;
-        const int32_t* d_mcu0 = d_crops + N * 5;
-        const JpegTables* d_tab = (const JpegTables*)(d_up + tab_at);
-
-        const int nblk = (int)(mcus * 6);
-        int16_t* coef = ar.get<int16_t>(1, (size_t)nblk * 64);
-        int32_t* mcu_crop = ar.get<int32_t>(2, (size_t)mcus);
-        int32_t* blk_bits = ar.get<int32_t>(3, (size_t)nblk);
-        int32_t* scan = ar.get<int32_t>(4, (size_t)nblk);
-        int32_t* lay = ar.get<int32_t>(5, 3 * (size_t)N + 1);  // bit0 [N], nbits [N], chunk0 [N + 1]
-        int32_t *bit0 = lay, *nbits = lay + N, *chunk0 = lay + 2 * N;
-        // results for the host: [0] chunks, then (bytes, 0xFF bytes) per crop
-        Arena::Mail res = ar.mail(1, (2 * (size_t)N + 1) * 4);
-        int32_t* h_res = (int32_t*)res.h;
-        int32_t* d_res = (int32_t*)res.d;
-
-        k_jpeg_mcu<<<(unsigned)mcus, 64, 0, st>>>(d_frames, frame_stride, row_stride, d_crops, d_mcu0, (int)N, d_tab,
-                                                  coef, mcu_crop);
-        k_jpeg_bits<<<cdiv(nblk, 4), 256, 0, st>>>(coef, mcu_crop, d_mcu0, d_tab, nblk, blk_bits);
-        VTF_HIP(hipGetLastError());
-        inclusive_scan_i32(ar, 6, blk_bits, scan, nblk, st);
-        k_jpeg_layout<<<cdiv(N + 1, 256), 256, 0, st>>>(scan, d_mcu0, (int)N, bit0, nbits, chunk0, d_res);
-        VTF_HIP(hipGetLastError());
-        VTF_HIP(hipStreamSynchronize(st));
-        const int nchunks = h_res[0];
-
-        uint32_t* words = ar.get<uint32_t>(7, (size_t)nchunks * CHUNK_WORDS + 2);  // (+2: a lane's window)
-        int32_t* chunk_ff = ar.get<int32_t>(8, (size_t)nchunks);
-        int32_t* ffscan = ar.get<int32_t>(9, (size_t)nchunks);
-        VTF_HIP(hipMemsetAsync(words, 0, ((size_t)nchunks * CHUNK_WORDS + 2) * 4, st));
-        k_jpeg_pack<<<cdiv(nblk, 4), 256, 0, st>>>(coef, mcu_crop, d_mcu0, d_tab, nblk, scan, bit0, nbits, chunk0,
-                                                   words);
-        k_jpeg_ffs<<<cdiv(nchunks, 4), 256, 0, st>>>(words, chunk0, nbits, (int)N, nchunks, chunk_ff);
-        VTF_HIP(hipGetLastError());
-        inclusive_scan_i32(ar, 6, chunk_ff, ffscan, nchunks, st);
-        k_jpeg_sizes<<<cdiv(N, 256), 256, 0, st>>>(ffscan, chunk0, nbits, (int)N, d_res + 1);
-        VTF_HIP(hipGetLastError());
-        VTF_HIP(hipStreamSynchronize(st));
-
-        int64_t total = 0;
-        for (int64_t i = 0; i < N; i++) {
-            total += JPEG_HEADER + (int64_t)h_res[1 + 2 * i] + h_res[2 + 2 * i] + 2;
-            out_offsets[i + 1] = total;
-        }
-        *out_total = total;
-        VTF_CHECK(total <= cap, VTF_E_CAPACITY, "jpeg output capacity too small (*out_total bytes needed)");
-        Arena::Mail off = ar.mail(2, ((size_t)N + 1) * 8);
-        std::memcpy(off.h, out_offsets, ((size_t)N + 1) * 8);
-        int64_t* d_off = ar.get<int64_t>(10, (size_t)N + 1);
-        VTF_HIP(hipMemcpyAsync(d_off, off.h, ((size_t)N + 1) * 8, hipMemcpyHostToDevice, st));
-        k_jpeg_stuff<<<cdiv(nchunks, 4), 256, 0, st>>>(words, chunk0, nbits, ffscan, d_off, (int)N, nchunks, d_out);
-        k_jpeg_header<<<(unsigned)N, 64, 0, st>>>(d_tab, d_crops, d_off, d_out);
-        VTF_HIP(hipGetLastError());
-        VTF_HIP(hipStreamSynchronize(st));
+extern "C" int vtf_jpeg_encode_crops_decoded(const uint8_t* d_frames, int F, int H, int W, int64_t frame_stride,
+                                             int64_t row_stride, const int32_t* crops, int64_t N, int quality,
+                                             uint8_t* d_out, int64_t cap, int64_t* out_offsets, int64_t* out_total,
+                                             uint8_t* d_pixels, int64_t pixels_cap, int32_t* out_status,
+                                             void* hip_stream) {
+    return guarded_on(stream_device((hipStream_t)hip_stream), [&] {
+        encode_crops(d_frames, F, H, W, frame_stride, row_stride, crops, N, quality, d_out, cap, out_offsets, out_total,
+                     true, d_pixels, pixels_cap, out_status, (hipStream_t)hip_stream);
     });
 }

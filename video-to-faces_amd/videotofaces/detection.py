@@ -180,13 +180,17 @@ class _HostFrame:
         return self.t[key].cpu().numpy()
 
 
-def process_frames_batch(frames, indices, model, det_params, save_params, hash_thr, hashes, jpeg_encoder='host'):
+def process_frames_batch(frames, indices, model, det_params, save_params, hash_thr, hashes, jpeg_encoder='host',
+                         store=None):
     """detection.py:126-158 with the frames uploaded to HBM once: detect and filter/adjust the
     boxes on device (detect_crops), average hashes of the crops on device, nearest-5 hash
     dedupe, JPEG save.  Returns (file names, updated `hashes` list).
     jpeg_encoder='device': the crops that survive the dedupe are encoded on the GPU in one call
     (utils.jpeg_encode_crops) and the files are written from the returned bytes; no crop's pixels
-    come to the host.  With resize_to set the host path is used: resizing stays on the host."""
+    come to the host.  With resize_to set the host path is used: resizing stays on the host.
+    store (a facestore.FaceStore, with the device encoder): the encoder also leaves every saved
+    face's decoded pixels in HBM, and the store keeps them under the file's path for encode_faces.
+    The files are written all the same.  The host path stores nothing."""
     import os.path as osp
     import numpy as np
     import torch
@@ -195,6 +199,10 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     from . import _native as nat
     if jpeg_encoder not in ('host', 'device'):
         raise ValueError("jpeg_encoder must be 'host' or 'device'")
+    if store is not None:
+        from .facestore import FaceStore
+        if not isinstance(store, FaceStore):
+            raise ValueError('store must be a FaceStore or None')
     _, mscore, msize, mborder, scale, square = det_params
     out_dir, out_prefix, resize_to, _, _, _ = save_params
     if isinstance(frames, torch.Tensor):  # frames already in HBM (a .y4m source; strided views are fine)
@@ -208,7 +216,7 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
         d_crops, _ = detect_crops(model, fr_dev, 0, mscore, msize, mborder, scale, square)
     rects = d_crops.cpu().numpy()
     if jpeg_encoder == 'device' and not resize_to:
-        return _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes), hashes
+        return _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes, store), hashes
     faces, seen = [], {}
     for fi, x1, y1, x2, y2 in rects.tolist():
         j = seen.get(fi, 0)
@@ -228,9 +236,11 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     return [fn for _, fn in faces], hashes
 
 
-def _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes):
+def _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes, store=None):
     """The hash dedupe and JPEG save of process_frames_batch with the encoder on the device:
-    file names and rectangles only on the host, one D2H of the compressed bytes."""
+    file names and rectangles only on the host, one D2H of the compressed bytes.  With a store the
+    faces' decoded pixels stay in HBM under their files' paths (those with status 0; a det-batch
+    that does not fit the store's budget is not stored)."""
     import os.path as osp
     from .dupes import ahash_crops, nearest_dupes
     from .utils import jpeg_encode_crops
@@ -244,16 +254,23 @@ def _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, ha
         flags, _ = nearest_dupes(list(zip(ahash_crops(fr_dev, rects), names)), hashes, hash_thr)
         keep = [i for i, d in zip(keep, flags) if not d]
     names = [names[i] for i in keep]
-    for fn, data in zip(names, jpeg_encode_crops(fr_dev, rects[keep], 95)):
+    kept = rects[keep]
+    if store is None or not names:
+        files = jpeg_encode_crops(fr_dev, kept, 95)
+    else:
+        files, pixels, offsets, status = jpeg_encode_crops(fr_dev, kept, 95, decoded=True)
+        store.add([osp.join(out_dir, 'faces', fn) for fn in names], pixels, offsets,
+                  np.stack([kept[:, 4] - kept[:, 2], kept[:, 3] - kept[:, 1]], 1), status == 0)
+    for fn, data in zip(names, files):
         with open(osp.join(out_dir, 'faces', fn), 'wb') as f:
             f.write(data)
     return names
 
 
-def detect_faces(files, model, vid_params, det_params, save_params, hash_thr, jpeg_encoder='host'):
+def detect_faces(files, model, vid_params, det_params, save_params, hash_thr, jpeg_encoder='host', store=None):
     """detection.py:32-65: every video in det-batches of sampled frames, then the overall hash
-    dedupe.  Saving annotated frames / rejects (debug IO) is not mirrored.  jpeg_encoder: see
-    process_frames_batch."""
+    dedupe.  Saving annotated frames / rejects (debug IO) is not mirrored.  jpeg_encoder, store: see
+    process_frames_batch; the faces the overall dedupe removes leave the store too."""
     import os
     import os.path as osp
     import numpy as np
@@ -281,12 +298,16 @@ def detect_faces(files, model, vid_params, det_params, save_params, hash_thr, jp
             if video_area:
                 cx1, cy1, cx2, cy2 = video_area
                 frames = frames[:, cy1:cy2, cx1:cx2, :]
-            fn_b, hashes = process_frames_batch(frames, bi, model, det_params, sp, hash_thr, hashes, jpeg_encoder)
+            fn_b, hashes = process_frames_batch(frames, bi, model, det_params, sp, hash_thr, hashes, jpeg_encoder, store)
             fnames.extend(fn_b)
         hashes_all.extend(h for (h, _) in hashes)  # the kept faces' hashes (detection.py:123)
     if hash_thr and hash_thr != -1 and fnames:
+        before = fnames
         _, fnames = remove_dupes_overall(np.stack([unpack_hash(h) for h in hashes_all]), fnames,
                                          ('hash', hash_thr, save_params[5], out_dir))
+        if store is not None:
+            left = set(fnames)
+            store.drop([osp.join(out_dir, 'faces', fn) for fn in before if fn not in left])
     paths = [osp.join(out_dir, 'faces', fn) for fn in fnames]
     print()
     print('Saved a total of %u faces to: %s' % (len(paths), osp.join(out_dir, 'faces')))

@@ -64,37 +64,81 @@ def _decode_group(paths, at):
     device does not decode, and oversize ones) and the atlas size.  A group ends at DECODE_GROUP
     files or before the file that would take the atlas past DECODE_ATLAS_BYTES; a file with a side
     above DECODE_MAX_SIDE is a group of its own.  Never empty."""
+    return _next_group(paths, at, None, 'device')[:5]
+
+
+def _next_group(paths, at, store, decoder):
+    """_decode_group with a face store: -> (files, probed, host, hm, wm, stored).  A path the store
+    holds is not opened: stored[index] is the store's (chunk, byte offset, h, w), its entry in
+    `files` is None and its size is the store's.  Any other path goes the way `decoder` says: read
+    and probed for 'device' as in _decode_group, read with _imread into `host` for 'host' (entry
+    None in `files`).  The group rules are the same for all of them."""
     from .utils import jpeg_probe
-    files, probed, host, hm, wm = [], [], {}, 1, 1
+    files, probed, host, stored, hm, wm = [], [], {}, {}, 1, 1
     while at + len(files) < len(paths) and len(files) < DECODE_GROUP:
         i = len(files)
-        with open(paths[at + i], 'rb') as f:
-            data = f.read()
-        h, w, kind = jpeg_probe(data)
-        img = None
-        if kind != 0 or max(h, w) > DECODE_MAX_SIDE:
-            img = _imread(paths[at + i])  # (fails here as it fails on the host path)
-            h, w = img.shape[:2]
+        ent = store.get(paths[at + i]) if store is not None else None
+        data = img = None
+        if ent is not None:
+            h, w, kind = ent[2], ent[3], 0
+        elif decoder == 'device':
+            with open(paths[at + i], 'rb') as f:
+                data = f.read()
+            h, w, kind = jpeg_probe(data)
+            if kind != 0 or max(h, w) > DECODE_MAX_SIDE:
+                img = _imread(paths[at + i])  # (fails here as it fails on the host path)
+                h, w = img.shape[:2]
+        else:
+            img = _imread(paths[at + i])
+            h, w, kind = img.shape[0], img.shape[1], 1
         big = max(h, w) > DECODE_MAX_SIDE
         if files and (big or (i + 1) * max(hm, h) * max(wm, w) * 3 > DECODE_ATLAS_BYTES):
             break  # this file starts the next group (nothing of it is kept here)
         if img is not None:
             host[i] = img
+        if ent is not None:
+            stored[i] = ent
         files.append(data)
         probed.append((h, w, kind))
         hm, wm = max(hm, h), max(wm, w)
         if big:
             break
-    return files, probed, host, hm, wm
+    return files, probed, host, hm, wm, stored
 
 
-def _encode_faces_device(paths, model, bs, area):
+def _gather_group(files, probed, host, hm, wm, stored, decoder, dev):
+    """The atlas of a group that has stored faces (or host-read files only): the stored faces by
+    one utils.faces_to_atlas launch, the files `decoder` = 'device' read by utils.jpeg_decode and
+    slot by slot into the same atlas.  -> (atlas, sizes, status) as utils.jpeg_decode gives them;
+    the slots of `host` are left for the caller."""
+    from .utils import faces_to_atlas, jpeg_decode
+    n = len(files)
+    sizes, status = np.array([p[:2] for p in probed], np.int32).reshape(-1, 2), np.zeros(n, np.int32)
+    faces = [None] * n
+    for i, (chunk, off, h, w) in stored.items():
+        faces[i] = chunk[off:off + h * w * 3]
+    atlas = faces_to_atlas(faces, sizes, hm, wm, dev)
+    rest = [i for i in range(n) if i not in stored and i not in host]
+    if rest:
+        sub, ssz, sst = jpeg_decode([files[i] for i in rest], dev, probed=[probed[i] for i in rest])
+        for j, i in enumerate(rest):
+            status[i] = sst[j]
+            if sst[j] == 0:
+                h, w = int(ssz[j, 0]), int(ssz[j, 1])
+                atlas[i, :h, :w] = sub[j, :h, :w]
+    return atlas, sizes, status
+
+
+def _encode_faces_device(paths, model, bs, area, store=None, decoder='device'):
     """encode_faces with the files decoded on the GPU (utils.jpeg_decode).  The files are decoded in
     groups (_decode_group), whatever `bs` is; every group's blobs come from the blob kernel
     model(images) runs, and the forward runs on the same batches of `bs` blobs in the same order, so
     the embeddings are the host path's bits.  A file the device does not decode (progressive,
     grayscale, corrupt, ...) or one with a side above DECODE_MAX_SIDE is read with _imread as on the
-    host path and copied into its slot of the group's one atlas."""
+    host path and copied into its slot of the group's one atlas.
+    store (a facestore.FaceStore): a path it holds is not opened at all; its decoded pixels are in
+    HBM already and go into its slot by utils.faces_to_atlas.  The other paths of such a run go the
+    way `decoder` says ('host': _imread, 'device': as above), into their slots of the same atlas."""
     from .utils import jpeg_decode
     dev = nat.device_of(model)
     x, pending = [], None  # blobs that wait for a full batch
@@ -108,10 +152,12 @@ def _encode_faces_device(paths, model, bs, area):
 
     at = 0
     while at < len(paths):
-        files, probed, host, hm, wm = _decode_group(paths, at)
+        files, probed, host, hm, wm, stored = _next_group(paths, at, store, decoder)
         if len(files) == 1 and host:  # one host-decoded file (an oversize one): its pixels are the atlas
             atlas = torch.from_numpy(np.ascontiguousarray(host[0])[None]).to(dev)
             sizes, status, host = np.array([host[0].shape[:2]], np.int32), np.zeros(1, np.int32), {}
+        elif stored or decoder != 'device':
+            atlas, sizes, status = _gather_group(files, probed, host, hm, wm, stored, decoder, dev)
         else:
             atlas, sizes, status = jpeg_decode(files, dev, probed=probed, min_size=(hm, wm))
         for i in np.flatnonzero(status != 0):
@@ -133,14 +179,21 @@ def _encode_faces_device(paths, model, bs, area):
     return np.concatenate(x)
 
 
-def encode_faces(paths, model, bs, area, jpeg_decoder='host'):
+def encode_faces(paths, model, bs, area, jpeg_decoder='host', store=None):
     """grouping.py:29-40: batches of images -> model -> concatenated [N, D].  jpeg_decoder='device'
     (an addition) decodes the files on the GPU instead of one by one on the host: the same pixels,
-    the same blob kernel and forward, the same embeddings."""
+    the same blob kernel and forward, the same embeddings.  store (an addition, a
+    facestore.FaceStore the detection stage filled): the faces it holds are taken from HBM and their
+    files are not opened; the rest go the way jpeg_decoder says.  The same embeddings again."""
+    from .facestore import FaceStore
     from .utils import crop_to_area
     if jpeg_decoder not in ('host', 'device'):
         raise ValueError("jpeg_decoder must be 'host' or 'device'")
+    if store is not None and not isinstance(store, FaceStore):
+        raise ValueError('store must be a FaceStore or None')
     print('Extracting features from images for grouping')
+    if store is not None and len(paths):
+        return _encode_faces_device(paths, model, bs, area, store, jpeg_decoder)
     if jpeg_decoder == 'device' and len(paths):
         return _encode_faces_device(paths, model, bs, area)
     x = []

@@ -22,7 +22,15 @@ and every all-pairs / K-means pass runs in libvtf_hip.so.  Additions, all opt-in
     libjpeg's pixels for baseline 4:2:0 files, a few hundred files per call, only the compressed
     bytes uploaded); 'host' (default) reads them one by one with OpenCV / Pillow as the reference
     does.  A file the device does not decode (progressive, grayscale, corrupt, ...) is read on the
-    host as before; the embeddings are the same bits either way.  Reference images stay on the host.
+    host as before; the embeddings are the same bits either way.  Reference images stay on the host;
+  * face_handoff='device' (mode='full' with jpeg_encoder='device') hands the faces from the
+    detection to the grouping stage in HBM: the device encoder also leaves what every file it writes
+    decodes to (vtf_jpeg_encode_crops_decoded, reconstructed from its own coefficients), a
+    facestore.FaceStore keeps those pixels, and encode_faces gathers them into its atlases
+    (vtf_faces_to_atlas) without opening a file.  The files are written as always; 'files'
+    (default) reads them back as jpeg_decoder says.  What does not fit the store's budget
+    (facestore.HANDOFF_BYTES), and every face of a run with resize_to, goes by file.  Other modes
+    ignore it; the multi-process path (parallel.py) does not use it.
 """
 import os.path as osp
 
@@ -70,7 +78,7 @@ def video_to_faces(input_path=None, input_ext=None,
                    enc_dup_thr=0.25, enc_oth_thr=0.9,
                    _test_enc=False, _test_exclude_other=False,
                    decoupled=False, det_precision='fp32', enc_precision='fp32', jpeg_encoder='host',
-                   jpeg_decoder='host'):
+                   jpeg_decoder='host', face_handoff='files'):
     from .detection import detect_faces
     from .dupes import remove_dupes_overall
     from .grouping import encode_faces, cluster_faces, classify_faces
@@ -80,6 +88,11 @@ def video_to_faces(input_path=None, input_ext=None,
     if not prep._one_of(jpeg_encoder, 'jpeg_encoder', ['host', 'device']):
         return
     if not prep._one_of(jpeg_decoder, 'jpeg_decoder', ['host', 'device']):
+        return
+    if not prep._one_of(face_handoff, 'face_handoff', ['files', 'device']):
+        return
+    if mode == 'full' and face_handoff == 'device' and jpeg_encoder != 'device':
+        print('ERROR: face_handoff="device" needs jpeg_encoder="device"')
         return
     if _test_enc:
         raise NotImplementedError('_test_enc needs a labels.txt ground truth (grouping.py:140-155)')
@@ -103,7 +116,10 @@ def video_to_faces(input_path=None, input_ext=None,
         refs = prep.get_class_ref(ref_dir, out_dir)
         if not refs:
             return
-    imgpaths = None
+    imgpaths, store = None, None
+    if mode == 'full' and face_handoff == 'device':
+        from .facestore import FaceStore
+        store = FaceStore()
     if mode == 'grouping':
         imgpaths = prep.get_paths_for_grouping(out_dir)
         if not imgpaths:
@@ -117,10 +133,13 @@ def video_to_faces(input_path=None, input_ext=None,
         save_params = (out_dir, out_prefix, resize_to, save_frames, save_rejects, save_dupes)
         detector = get_detector(style, det_model, device, det_precision)
         imgpaths = detect_faces(files, detector, vid_params, det_params, save_params, hash_thr,
-                                jpeg_encoder=jpeg_encoder)
+                                jpeg_encoder=jpeg_encoder, store=store)
     if mode in ('full', 'grouping') and imgpaths:
         encoder = get_encoder(style, enc_model, device, enc_precision)
-        features = encode_faces(imgpaths, encoder, enc_batch_size, enc_area, jpeg_decoder=jpeg_decoder)
+        features = encode_faces(imgpaths, encoder, enc_batch_size, enc_area, jpeg_decoder=jpeg_decoder, store=store)
+        if store is not None:  # the dedupe and the clustering get the memory back
+            store.clear()
+            store = None
         if enc_dup_thr and enc_dup_thr != -1:
             features, imgpaths = remove_dupes_overall(features, imgpaths, ('enc', enc_dup_thr, save_dupes, out_dir),
                                                       device=device)

@@ -66,12 +66,16 @@ def imwrite(path, img):
         return True
 
 
-def jpeg_encode_crops(frames_dev, crops, quality=95):
+def jpeg_encode_crops(frames_dev, crops, quality=95, decoded=False):
     """cv2.imwrite of every crop (int [N,5] frame, x1, y1, x2, y2) of the CUDA uint8 BGR frames
     [B,H,W,3] on the device (vtf_jpeg_encode_crops) -> list of N `bytes`, each a whole baseline
     JPEG file with the bytes libjpeg writes at `quality` (what Pillow's save(quality=) gives for
     the crop's RGB pixels).  One library call (a second one with the exact size when the first
-    guess of the output capacity was too small) and one D2H copy of the bytes used."""
+    guess of the output capacity was too small) and one D2H copy of the bytes used.
+    decoded=True (vtf_jpeg_encode_crops_decoded) -> (files, pixels, offsets, status): the same
+    files, and what cv2.imread gives for each of them, left in HBM: `pixels` a CUDA uint8 1-D tensor
+    with crop i's BGR [h][w][3] at pixels[offsets[i]:offsets[i+1]] (offsets np.int64 [N+1]), status
+    np.int32 [N]: 0, or 2 for a crop whose pixels are not valid (never for 8-bit frames)."""
     import ctypes
     import numpy as np
     import torch
@@ -79,32 +83,77 @@ def jpeg_encode_crops(frames_dev, crops, quality=95):
     if not (isinstance(frames_dev, torch.Tensor) and frames_dev.is_cuda and frames_dev.dtype == torch.uint8
             and frames_dev.dim() == 4 and frames_dev.shape[3] == 3):
         raise ValueError('frames must be a CUDA uint8 tensor [B,H,W,3]')
+    if not isinstance(decoded, bool):
+        raise ValueError('decoded must be True or False')
     crops = np.ascontiguousarray(np.asarray(crops, np.int32).reshape(-1, 5))
     n = crops.shape[0]
+    dev = frames_dev.device
     if n == 0:
+        if decoded:
+            return [], torch.empty(0, dtype=torch.uint8, device=dev), np.zeros(1, np.int64), np.zeros(0, np.int32)
         return []
     if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
         frames_dev = frames_dev.contiguous()
     B, H, W = frames_dev.shape[:3]
-    dev = frames_dev.device
     offs = np.zeros(n + 1, np.int64)
     total = ctypes.c_int64(0)
     # first guess: the header and a byte per pixel (quality 95 photographs need about half that)
     w, h = (crops[:, 3] - crops[:, 1]).astype(np.int64), (crops[:, 4] - crops[:, 2]).astype(np.int64)
     cap = int((1024 + np.maximum(w, 0) * np.maximum(h, 0)).sum())
+    poffs = np.zeros(n + 1, np.int64)
+    np.cumsum(np.maximum(w, 0) * np.maximum(h, 0) * 3, out=poffs[1:])
+    status = np.zeros(n, np.int32)
     with torch.cuda.device(dev):
+        pixels = torch.empty(int(poffs[n]), dtype=torch.uint8, device=dev) if decoded else None
         for attempt in (0, 1):
             out = torch.empty(cap, dtype=torch.uint8, device=dev)
-            rc = nat.lib().vtf_jpeg_encode_crops(nat.ptr(frames_dev), B, H, W, frames_dev.stride(0),
-                                                 frames_dev.stride(1), crops.ctypes.data, n, int(quality),
-                                                 nat.ptr(out), cap, offs.ctypes.data, ctypes.byref(total),
-                                                 nat.stream_ptr(dev))
+            args = (nat.ptr(frames_dev), B, H, W, frames_dev.stride(0), frames_dev.stride(1), crops.ctypes.data, n,
+                    int(quality), nat.ptr(out), cap, offs.ctypes.data, ctypes.byref(total))
+            if decoded:
+                rc = nat.lib().vtf_jpeg_encode_crops_decoded(*args, nat.ptr(pixels), pixels.numel(),
+                                                             status.ctypes.data, nat.stream_ptr(dev))
+            else:
+                rc = nat.lib().vtf_jpeg_encode_crops(*args, nat.stream_ptr(dev))
             if rc != nat.VTF_E_CAPACITY or attempt:
                 break
             cap = int(total.value)
     nat.check(rc)
     data = out[:int(offs[n])].cpu().numpy().tobytes()
-    return [data[offs[i]:offs[i + 1]] for i in range(n)]
+    files = [data[offs[i]:offs[i + 1]] for i in range(n)]
+    return (files, pixels, poffs, status) if decoded else files
+
+
+def faces_to_atlas(faces, sizes, hm, wm, device):
+    """Faces that lie in HBM into the slots of an atlas (vtf_faces_to_atlas): `faces` a list of N
+    CUDA uint8 tensors (any view whose h * w * 3 bytes are contiguous: a slice of jpeg_encode_crops'
+    `pixels`) or None, `sizes` int [N,2] (h, w).  -> CUDA uint8 [N,hm,wm,3] with face i in
+    atlas[i, :h, :w]; the rest of a slot, and the whole slot of a None entry, is not written (the
+    caller fills it).  One launch for all faces."""
+    import ctypes
+    import numpy as np
+    import torch
+    from . import _native as nat
+    dev = nat.require_gpu(device)
+    sizes = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(-1, 2))
+    n = len(faces)
+    if sizes.shape[0] != n:
+        raise ValueError('sizes must be [N,2] for N faces')
+    hm, wm = int(hm), int(wm)
+    atlas = torch.empty((n, hm, wm, 3), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return atlas
+    ptrs = (ctypes.c_void_p * n)()
+    for i, f in enumerate(faces):
+        if f is None:
+            continue
+        if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous()
+                and f.device == atlas.device and f.numel() == int(sizes[i, 0]) * int(sizes[i, 1]) * 3):
+            raise ValueError('face %d must be a contiguous CUDA uint8 tensor of h * w * 3 bytes on %s' % (i, atlas.device))
+        ptrs[i] = f.data_ptr()
+    with torch.cuda.device(atlas.device):
+        nat.check(nat.lib().vtf_faces_to_atlas(ctypes.cast(ptrs, ctypes.c_void_p), sizes.ctypes.data, n, nat.ptr(atlas),
+                                               hm, wm, atlas.stride(0), atlas.stride(1), nat.stream_ptr(atlas.device)))
+    return atlas
 
 
 def jpeg_probe(data):
