@@ -288,6 +288,22 @@ int vtf_jpeg_decode(const uint8_t* data, const int64_t* offsets, int64_t N, uint
  * the stream is synchronised.  Scratch: the stream's arena (vtf_release_stream). */
 int vtf_faces_to_atlas(const uint8_t* const* faces, const int32_t* sizes, int64_t N, uint8_t* d_atlas, int Hmax,
                        int Wmax, int64_t frame_stride, int64_t row_stride, void* hip_stream);
+/* cv2.resize(crop, (w, h)) INTER_LINEAR of resize_keep_ratio (utils/image.py:4-14, detection.py:147-148)
+ * for N crops of device frames into the slots of such a buffer.  frames / crops (host int32 [N,5],
+ * validated) as in vtf_ahash_crops; sizes host int32 [N,2] = the destination (h, w) of every crop.
+ * Crop i is resampled to sizes[i] and written to rows < h and columns < w of slot i of d_atlas
+ * [N][Hmax][Wmax][3] at the given strides (bytes); nothing else of a slot is written.  The pixels
+ * are OpenCV's uint8 fixed point (11-bit coefficients) as utils.resize_linear restates it, bit for
+ * bit; a destination equal to the source size copies the crop; an exact 2x downscale is
+ * INTER_LINEAR too (no INTER_AREA substitution).  The atlas with the rectangles (i, 0, 0, w, h) is
+ * a valid frames / crops input of vtf_ahash_crops and vtf_jpeg_encode_crops.  One launch.
+ * VTF_E_ARG: null pointers, N < 0, a destination side < 1 or above Hmax / Wmax, an empty source
+ * crop or one outside the frames, a bad frame index, atlas strides too small (vtf_jpeg_decode's
+ * rule); nothing is written then.  N = 0 is fine and launches nothing.  Returns after the stream
+ * is synchronised.  Scratch: the stream's arena (vtf_release_stream). */
+int vtf_resize_crops(const uint8_t* d_frames, int F, int H, int W, int64_t frame_stride, int64_t row_stride,
+                     const int32_t* crops, const int32_t* sizes, int64_t N, uint8_t* d_atlas, int Hmax, int Wmax,
+                     int64_t atlas_frame_stride, int64_t atlas_row_stride, void* hip_stream);
 /* Stage timing of vtf_jpeg_decode on the calling thread: enable != 0 makes later calls bracket
  * their kernels with HIP events; out_ms (may be null) receives the last timed call's
  * (entropy decode, IDCT + upsampling + colour) milliseconds. */

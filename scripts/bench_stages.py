@@ -12,6 +12,12 @@
             host = one .cpu().numpy() slice per crop + utils.imwrite (the jpeg_encoder='host'
             path), device = utils.jpeg_encode_crops + writing the same files.  ms per det-batch,
             the ratio and the bytes each moves D2H.
+  resize    the same det-batch written with resize_to=160 (detection.py:147-158): jpeg's frames and
+            rectangles.  host = one .cpu().numpy() slice per crop + utils.resize_keep_ratio +
+            dupes.ahash of the resized face (an upload and a launch per face) + utils.imwrite,
+            device = utils.resize_crops + dupes.ahash_crops + utils.jpeg_encode_crops on the atlas +
+            writing the files; resize_only = utils.resize_crops alone.  ms per det-batch, the
+            copies and bytes each moves, and whether the two legs wrote the same files.
   jpeg_decode  the face-file read of the grouping stage (grouping.py:29-40): about 1,024 face files
             written by the device encoder from device-generated 720p frames and the crops
             detect_crops gives for them.  Two legs in one process: host = encode_faces' path up to
@@ -33,6 +39,7 @@ reference's own grouping dependency), on bounded samples, timed on this host's c
   python scripts/bench_stages.py vit [--vit-model vit_l] [--steps 10] [--warmup 2]
   python scripts/bench_stages.py grouping [--n 10000] [--d 512]
   python scripts/bench_stages.py jpeg [--steps 20] [--warmup 3]
+  python scripts/bench_stages.py resize [--steps 20] [--warmup 3]
   python scripts/bench_stages.py jpeg_decode [--steps 10] [--warmup 3]
   python scripts/bench_stages.py handoff [--steps 10] [--warmup 3]
 """
@@ -168,12 +175,11 @@ def bench_grouping(a):
     print(json.dumps(res), flush=True)
 
 
-def bench_jpeg(a):
-    import tempfile
+def jpeg_inputs():
+    """The det-batch of the jpeg and resize stages -> (frames in HBM, rectangles, where they come from)"""
     from videotofaces import synth
     from videotofaces.detection import detect_crops
     from videotofaces.detectors.mtcnn import RealMTCNN
-    from videotofaces.utils import imwrite, jpeg_encode_crops
     dev = torch.device('cuda:0')
     B, H, W = 16, 720, 1280
     frames = synth.make_frames_device(0, B, H, W, seed=0, device=dev, style='blobs')
@@ -193,6 +199,14 @@ def bench_jpeg(a):
             rects.append([i % B, x, y, x + w, y + h])
         rects = np.array(rects, np.int32)
         source = 'fixed list (seeded): 48 rectangles of 100-250 px'
+    return frames, rects, source
+
+
+def bench_jpeg(a):
+    import tempfile
+    from videotofaces.utils import imwrite, jpeg_encode_crops
+    frames, rects, source = jpeg_inputs()
+    dev = frames.device
     n = len(rects)
     names = ['%06d.jpg' % i for i in range(n)]
 
@@ -243,6 +257,82 @@ def bench_jpeg(a):
            'd2h_bytes': {'host': pix * 3, 'device': sizes['device']},
            'd2h_copies': {'host': n, 'device': 1},
            'file_bytes': sizes, 'files_identical_size': sizes['host'] == sizes['device']}
+    print(json.dumps(res), flush=True)
+
+
+def bench_resize(a):
+    import tempfile
+    from videotofaces.dupes import ahash, ahash_crops
+    from videotofaces.utils import imwrite, jpeg_encode_crops, resize_crops, resize_keep_ratio, resize_sizes
+    to = 160
+    frames, rects, source = jpeg_inputs()
+    dev = frames.device
+    n = len(rects)
+    names = ['%06d.jpg' % i for i in range(n)]
+
+    def host_leg(d):  # process_frames_batch with resize_to before the device path took it
+        faces = [resize_keep_ratio(frames[fi][y1:y2, x1:x2].cpu().numpy(), to) for fi, x1, y1, x2, y2 in rects.tolist()]
+        hs = [ahash(img, dev) for img in faces]
+        for img, fn in zip(faces, names):
+            imwrite(os.path.join(d, fn), np.ascontiguousarray(img))
+        return hs
+
+    def device_leg(d):
+        atlas, sizes = resize_crops(frames, rects, to)
+        slots = np.zeros((n, 5), np.int32)
+        slots[:, 0], slots[:, 3], slots[:, 4] = np.arange(n), sizes[:, 1], sizes[:, 0]
+        hs = ahash_crops(atlas, slots)
+        for data, fn in zip(jpeg_encode_crops(atlas, slots, 95), names):
+            with open(os.path.join(d, fn), 'wb') as f:
+                f.write(data)
+        return hs
+
+    def resize_only(d):
+        resize_crops(frames, rects, to)
+
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for leg, fn in (('host', host_leg), ('device', device_leg), ('resize_only', resize_only)):
+            d = os.path.join(tmp, leg)
+            os.makedirs(d)
+            for _ in range(a.warmup):
+                fn(d)
+            torch.cuda.synchronize(dev)
+            ts = []
+            for _ in range(a.steps):
+                t0 = time.perf_counter()
+                fn(d)
+                torch.cuda.synchronize(dev)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            out[leg] = ts
+        files = {leg: [open(os.path.join(tmp, leg, f), 'rb').read() for f in names] for leg in ('host', 'device')}
+    try:
+        import cv2  # noqa: F401
+        writer = 'cv2.imwrite'
+    except ImportError:
+        writer = 'Pillow save(quality=95)'
+    pix = int(((rects[:, 3] - rects[:, 1]).astype(np.int64) * (rects[:, 4] - rects[:, 2])).sum())
+    dst = np.asarray(resize_sizes([(r[4] - r[2], r[3] - r[1]) for r in rects.tolist()], to), np.int64)
+    dpix = int((dst[:, 0] * dst[:, 1]).sum())
+    med = {k: float(np.median(v)) for k, v in out.items()}
+    fbytes = {leg: sum(len(f) for f in v) for leg, v in files.items()}
+    res = {'metric': 'resized face write, ms per det-batch (16 x 720p frames, %d crops, resize_to %d, hashes, '
+                     'quality 95)' % (n, to),
+           'value': round(med['device'], 3), 'unit': 'ms', 'higher_is_better': False, 'n_gpus': 1,
+           'steps': a.steps, 'warmup': a.warmup, 'data': 'synthetic (device-generated blobs frames, seed 0)',
+           'config': {'crops': n, 'crop_source': source, 'crop_pixels': pix, 'resize_to': to, 'resized_pixels': dpix,
+                      'atlas_bytes': int(n * dst[:, 0].max() * dst[:, 1].max() * 3), 'host_writer': writer,
+                      'host_cores_used': 1},
+           'host_ms': round(med['host'], 3), 'host_ms_min': round(min(out['host']), 3),
+           'device_ms': round(med['device'], 3), 'device_ms_min': round(min(out['device']), 3),
+           'resize_only_ms': round(med['resize_only'], 3), 'resize_only_ms_min': round(min(out['resize_only']), 3),
+           'host_over_device': round(med['host'] / med['device'], 2),
+           # host: a slice and a hash word per crop; device: the hash words and the files' bytes
+           'd2h_copies': {'host': 2 * n, 'device': 2},
+           'd2h_bytes': {'host': pix * 3 + 8 * n, 'device': 8 * n + fbytes['device']},
+           'h2d_pixel_copies': {'host': n, 'device': 0}, 'h2d_pixel_bytes': {'host': dpix * 3, 'device': 0},
+           'file_bytes': fbytes, 'files_identical': files['host'] == files['device'],
+           'whole_run_measured': False}
     print(json.dumps(res), flush=True)
 
 
@@ -508,7 +598,7 @@ def bench_handoff(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg', 'jpeg_decode', 'handoff'])
+    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg', 'resize', 'jpeg_decode', 'handoff'])
     ap.add_argument('--vit-model', default='vit_l', choices=['vit_b', 'vit_l'])
     ap.add_argument('--vit-precision', default='f16x', choices=['fp32', 'f16x'])
     ap.add_argument('--enc-batch', type=int, default=128)
@@ -521,8 +611,8 @@ def main():
     ap.add_argument('--cpu-ks', type=int, default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
-    {'vit': bench_vit, 'grouping': bench_grouping, 'jpeg': bench_jpeg, 'jpeg_decode': bench_jpeg_decode,
-     'handoff': bench_handoff}[a.stage](a)
+    {'vit': bench_vit, 'grouping': bench_grouping, 'jpeg': bench_jpeg, 'resize': bench_resize,
+     'jpeg_decode': bench_jpeg_decode, 'handoff': bench_handoff}[a.stage](a)
 
 
 if __name__ == '__main__':

@@ -90,6 +90,7 @@ SIGNATURES = {
     'vtf_jpeg_encode_crops_decoded': [_p, _i32, _i32, _i32, _i64, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i64, _p,
                                       _p],
     'vtf_faces_to_atlas': [_p, _p, _i64, _p, _i32, _i32, _i64, _i64, _p],
+    'vtf_resize_crops': [_p, _i32, _i32, _i32, _i64, _i64, _p, _p, _i64, _p, _i32, _i32, _i64, _i64, _p],
     'vtf_jpeg_probe': [_p, _i64, _p],
     'vtf_jpeg_decode': [_p, _p, _i64, _p, _i32, _i32, _i64, _i64, _p, _p, _p],
     'vtf_jpeg_decode_profile': [_i32, _p],

@@ -187,7 +187,11 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     dedupe, JPEG save.  Returns (file names, updated `hashes` list).
     jpeg_encoder='device': the crops that survive the dedupe are encoded on the GPU in one call
     (utils.jpeg_encode_crops) and the files are written from the returned bytes; no crop's pixels
-    come to the host.  With resize_to set the host path is used: resizing stays on the host.
+    come to the host.  With resize_to set the crops are first resized on the GPU
+    (utils.resize_crops) into an atlas, and the hashes and the files are made from its slots: the
+    names, the hashes and the bytes are the host path's.  A det-batch with a rectangle whose resized
+    face would have a zero side (the host path raises for it), or whose atlas would exceed
+    RESIZE_ATLAS_BYTES, takes the host path.
     store (a facestore.FaceStore, with the device encoder): the encoder also leaves every saved
     face's decoded pixels in HBM, and the store keeps them under the file's path for encode_faces.
     The files are written all the same.  The host path stores nothing."""
@@ -215,8 +219,9 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     with torch.inference_mode():
         d_crops, _ = detect_crops(model, fr_dev, 0, mscore, msize, mborder, scale, square)
     rects = d_crops.cpu().numpy()
-    if jpeg_encoder == 'device' and not resize_to:
-        return _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes, store), hashes
+    if jpeg_encoder == 'device' and (not resize_to or _resize_on_device(rects, resize_to)):
+        return _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes, store,
+                                  resize_to), hashes
     faces, seen = [], {}
     for fi, x1, y1, x2, y2 in rects.tolist():
         j = seen.get(fi, 0)
@@ -236,19 +241,50 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     return [fn for _, fn in faces], hashes
 
 
-def _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes, store=None):
+# The largest atlas of resized faces process_frames_batch makes for one det-batch: 1 GiB, the
+# meaning of grouping.DECODE_ATLAS_BYTES (every slot has the largest face's size; a det-batch of
+# 160 x 160 faces takes 75 KiB a face).  A det-batch past it takes the host path.
+RESIZE_ATLAS_BYTES = 1 << 30
+
+
+def _resize_on_device(rects, resize_to):
+    """Can utils.resize_crops resize these rectangles?  Not with a resize_to it does not take (the
+    host path then does what it always did with it), an empty rectangle or a resized face with a
+    zero side (the host path raises), or an atlas past RESIZE_ATLAS_BYTES."""
+    from .utils import is_to_area, resize_sizes
+    if not is_to_area(resize_to):
+        return False
+    if len(rects) == 0:
+        return True
+    hw = np.stack([rects[:, 4] - rects[:, 2], rects[:, 3] - rects[:, 1]], 1)
+    if (hw < 1).any():
+        return False
+    sizes = np.asarray(resize_sizes(hw.tolist(), resize_to), np.int64)
+    if (sizes < 1).any():
+        return False
+    return len(rects) * int(sizes[:, 0].max()) * int(sizes[:, 1].max()) * 3 <= RESIZE_ATLAS_BYTES
+
+
+def _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes, store=None, resize_to=None):
     """The hash dedupe and JPEG save of process_frames_batch with the encoder on the device:
     file names and rectangles only on the host, one D2H of the compressed bytes.  With a store the
     faces' decoded pixels stay in HBM under their files' paths (those with status 0; a det-batch
-    that does not fit the store's budget is not stored)."""
+    that does not fit the store's budget is not stored).  With resize_to the faces are the slots
+    of utils.resize_crops' atlas, which then stands for the frames: slot i with the rectangle
+    (i, 0, 0, w, h) is hashed (the reference hashes the resized face, detection.py:149-153) and
+    encoded."""
     import os.path as osp
     from .dupes import ahash_crops, nearest_dupes
-    from .utils import jpeg_encode_crops
+    from .utils import jpeg_encode_crops, resize_crops
     names, seen = [], {}
     for fi in rects[:, 0].tolist():
         j = seen.get(fi, 0)
         seen[fi] = j + 1
         names.append(out_prefix + '%06d_%u.jpg' % (indices[fi], j))
+    if resize_to and names:
+        fr_dev, sizes = resize_crops(fr_dev, rects, resize_to)
+        rects = np.zeros((len(names), 5), np.int32)
+        rects[:, 0], rects[:, 3], rects[:, 4] = np.arange(len(names)), sizes[:, 1], sizes[:, 0]
     keep = list(range(len(names)))
     if hash_thr and hash_thr != -1 and names:
         flags, _ = nearest_dupes(list(zip(ahash_crops(fr_dev, rects), names)), hashes, hash_thr)

@@ -16,8 +16,9 @@ and every all-pairs / K-means pass runs in libvtf_hip.so.  Additions, all opt-in
   * jpeg_encoder='device' encodes the face JPEGs of a det-batch on the GPU
     (vtf_jpeg_encode_crops: libjpeg's baseline 4:2:0 bytes at quality 95) and brings only the
     compressed bytes to the host in one copy; 'host' (default) slices every crop to the host and
-    writes it with OpenCV / Pillow as the reference does.  With resize_to set, 'device' uses
-    the host path for that call: resizing stays on the host;
+    writes it with OpenCV / Pillow as the reference does.  With resize_to set, 'device' first
+    resizes the crops on the GPU (vtf_resize_crops: the host path's INTER_LINEAR pixels) and
+    hashes and encodes the resized faces there; the files are the host path's, byte for byte;
   * jpeg_decoder='device' decodes the face files for grouping on the GPU (vtf_jpeg_decode:
     libjpeg's pixels for baseline 4:2:0 files, a few hundred files per call, only the compressed
     bytes uploaded); 'host' (default) reads them one by one with OpenCV / Pillow as the reference
@@ -29,7 +30,7 @@ and every all-pairs / K-means pass runs in libvtf_hip.so.  Additions, all opt-in
     facestore.FaceStore keeps those pixels, and encode_faces gathers them into its atlases
     (vtf_faces_to_atlas) without opening a file.  The files are written as always; 'files'
     (default) reads them back as jpeg_decoder says.  What does not fit the store's budget
-    (facestore.HANDOFF_BYTES), and every face of a run with resize_to, goes by file.  Other modes
+    (facestore.HANDOFF_BYTES) goes by file.  Other modes
     ignore it; the multi-process path (parallel.py) does not use it.
 """
 import os.path as osp

@@ -10,14 +10,39 @@ def crop_to_area(img, area):
     return img[y1:y2, x1:x2, :]
 
 
-def resize_keep_ratio(img, to_area, upscale=True):
-    """utils/image.py:4-14 (cv2.resize INTER_LINEAR restated on the host, uint8 fixed point)."""
-    h, w = img.shape[:2]
+def _keep_ratio(h, w, to_area, upscale):
+    """The (h, w) resize_keep_ratio resizes an h x w image to, or None when it leaves it alone."""
     aw, ah = to_area if isinstance(to_area, tuple) else (to_area, to_area)
     scale = min(aw / w, ah / h)
     if scale != 1 and (upscale or scale < 1):
-        img = resize_linear(img, int(h * scale), int(w * scale))
+        return int(h * scale), int(w * scale)
+    return None
+
+
+def resize_keep_ratio(img, to_area, upscale=True):
+    """utils/image.py:4-14 (cv2.resize INTER_LINEAR restated on the host, uint8 fixed point)."""
+    h, w = img.shape[:2]
+    to = _keep_ratio(h, w, to_area, upscale)
+    if to is not None:
+        img = resize_linear(img, to[0], to[1])
     return img
+
+
+def is_to_area(to_area):
+    """Is this a to_area the device path takes: a positive int or a tuple of two (aw, ah)?"""
+    import numbers
+
+    def positive(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool) and v > 0
+    return positive(to_area) or (isinstance(to_area, tuple) and len(to_area) == 2 and positive(to_area[0])
+                                 and positive(to_area[1]))
+
+
+def resize_sizes(hw, to_area, upscale=True):
+    """resize_keep_ratio(img, to_area, upscale).shape[:2] for every (h, w) of `hw`, without the
+    images -> list of (h, w).  The same Python float expression (_keep_ratio), so the two cannot
+    disagree; a side may come out 0 (a 1 x 500 image to 100), which resize_keep_ratio cannot resize."""
+    return [_keep_ratio(int(h), int(w), to_area, upscale) or (int(h), int(w)) for h, w in hw]
 
 
 def _lin_coefs(src, dst):
@@ -154,6 +179,52 @@ def faces_to_atlas(faces, sizes, hm, wm, device):
         nat.check(nat.lib().vtf_faces_to_atlas(ctypes.cast(ptrs, ctypes.c_void_p), sizes.ctypes.data, n, nat.ptr(atlas),
                                                hm, wm, atlas.stride(0), atlas.stride(1), nat.stream_ptr(atlas.device)))
     return atlas
+
+
+def resize_crops(frames_dev, crops, to_area, upscale=True):
+    """resize_keep_ratio(crop, to_area, upscale) of every crop (int [N,5] frame, x1, y1, x2, y2) of
+    the CUDA uint8 BGR frames [B,H,W,3] on the device (vtf_resize_crops) -> (atlas, sizes): a CUDA
+    uint8 tensor [N,Hmax,Wmax,3] with the resized crop i in atlas[i, :h, :w] (the rest of a slot
+    is not written), and np.int32 [N,2] (h, w) = resize_sizes of the crops; Hmax / Wmax are the
+    largest h / w.  The pixels are resize_linear's, bit for bit.  The atlas with the rectangles
+    (i, 0, 0, w, h) is an input of dupes.ahash_crops and jpeg_encode_crops.  to_area: a positive
+    int or a pair of positive ints (aw, ah).  One library call, no copy to the host.  A crop whose
+    destination has a zero side (a 1 x 500 crop to 100) raises ValueError."""
+    import numpy as np
+    import torch
+    from . import _native as nat
+
+    if isinstance(to_area, list):
+        to_area = tuple(to_area)
+    if not is_to_area(to_area):
+        raise ValueError('to_area must be a positive int or a pair of positive ints (aw, ah)')
+    if not isinstance(upscale, bool):
+        raise ValueError('upscale must be True or False')
+    crops = np.ascontiguousarray(np.asarray(crops, np.int32).reshape(-1, 5))
+    n = crops.shape[0]
+    src = np.stack([crops[:, 4] - crops[:, 2], crops[:, 3] - crops[:, 1]], 1)
+    if (src < 1).any():
+        raise ValueError('crop %d is empty' % int(np.nonzero((src < 1).any(1))[0][0]))
+    sizes = np.asarray(resize_sizes(src.tolist(), to_area, upscale), np.int32).reshape(-1, 2)
+    if (sizes < 1).any():
+        i = int(np.nonzero((sizes < 1).any(1))[0][0])
+        raise ValueError('crop %d (%d x %d) resized to %s has a zero side' % (i, src[i, 0], src[i, 1], to_area))
+    if not (isinstance(frames_dev, torch.Tensor) and frames_dev.is_cuda and frames_dev.dtype == torch.uint8
+            and frames_dev.dim() == 4 and frames_dev.shape[3] == 3):
+        raise ValueError('frames must be a CUDA uint8 tensor [B,H,W,3]')
+    dev = frames_dev.device
+    if n == 0:
+        return torch.empty((0, 1, 1, 3), dtype=torch.uint8, device=dev), sizes
+    if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
+        frames_dev = frames_dev.contiguous()
+    B, H, W = frames_dev.shape[:3]
+    hm, wm = int(sizes[:, 0].max()), int(sizes[:, 1].max())
+    with torch.cuda.device(dev):
+        atlas = torch.empty((n, hm, wm, 3), dtype=torch.uint8, device=dev)
+        nat.check(nat.lib().vtf_resize_crops(nat.ptr(frames_dev), B, H, W, frames_dev.stride(0), frames_dev.stride(1),
+                                             crops.ctypes.data, sizes.ctypes.data, n, nat.ptr(atlas), hm, wm,
+                                             atlas.stride(0), atlas.stride(1), nat.stream_ptr(dev)))
+    return atlas, sizes
 
 
 def jpeg_probe(data):
