@@ -279,6 +279,17 @@ int vtf_jpeg_probe(const uint8_t* data, int64_t len, int32_t* info);
 int vtf_jpeg_decode(const uint8_t* data, const int64_t* offsets, int64_t N, uint8_t* d_bgr, int Hmax, int Wmax,
                     int64_t frame_stride, int64_t row_stride, int32_t* out_sizes, int32_t* out_status,
                     void* hip_stream);
+/* vtf_jpeg_decode with a stage 1 made for long scans (video frames): every file's scan is cut
+ * into segments of seg_bytes (after removing the stuffed zero bytes) and decoded by as many lanes of
+ * one workgroup, which find their decoder states by speculation and re-synchronisation
+ * (csrc/jpeg_entropy_split.hpp); stage 2 is the same.  The contract is vtf_jpeg_decode's: the same
+ * classification on the host, sizes, statuses, slot rules, zero-fill of a corrupt file's slot and
+ * argument errors; N = 0 is fine; returns after the stream is synchronised.  seg_bytes: 0 = the
+ * library's default (128), otherwise a multiple of 4 in [4, 4096], else VTF_E_ARG.  The pixels do
+ * not depend on seg_bytes. */
+int vtf_jpeg_decode_split(const uint8_t* data, const int64_t* offsets, int64_t N, uint8_t* d_bgr, int Hmax, int Wmax,
+                          int64_t frame_stride, int64_t row_stride, int32_t* out_sizes, int32_t* out_status,
+                          int seg_bytes, void* hip_stream);
 /* Faces that are in HBM already into the slots of such a buffer: faces host array [N] of device
  * pointers to tight [h][w][3] pixels (vtf_jpeg_encode_crops_decoded's), sizes host int32 [N,2] =
  * (h, w); face i is copied to rows < h and columns < w of slot i of d_atlas [N][Hmax][Wmax][3] at
@@ -304,9 +315,9 @@ int vtf_faces_to_atlas(const uint8_t* const* faces, const int32_t* sizes, int64_
 int vtf_resize_crops(const uint8_t* d_frames, int F, int H, int W, int64_t frame_stride, int64_t row_stride,
                      const int32_t* crops, const int32_t* sizes, int64_t N, uint8_t* d_atlas, int Hmax, int Wmax,
                      int64_t atlas_frame_stride, int64_t atlas_row_stride, void* hip_stream);
-/* Stage timing of vtf_jpeg_decode on the calling thread: enable != 0 makes later calls bracket
- * their kernels with HIP events; out_ms (may be null) receives the last timed call's
- * (entropy decode, IDCT + upsampling + colour) milliseconds. */
+/* Stage timing of vtf_jpeg_decode and vtf_jpeg_decode_split on the calling thread: enable != 0
+ * makes later calls bracket their kernels with HIP events; out_ms (may be null) receives the last
+ * timed call's (entropy decode, IDCT + upsampling + colour) milliseconds. */
 int vtf_jpeg_decode_profile(int enable, float* out_ms);
 
 /* ---------------------------------------------------------------- video frames

@@ -32,6 +32,13 @@
             from the store, in groups of grouping.DECODE_GROUP (no file opened).  ms per 1,024
             faces and the ratios; also the encode call of one det-batch with decoded=False and
             decoded=True (the surcharge the detection stage pays for the stored pixels).
+  mjpeg     reading one det-batch of a Motion-JPEG file (video.MJPEGReader): 16 device-generated
+            720p frames, encoded once with Pillow at quality 90 into an AVI file.  Three legs in one
+            process, each from the memory-mapped file to BGR frames in HBM: host = read(decoder=
+            'host') (Pillow on one core + one upload), serial = utils.jpeg_decode(scan='serial') on
+            the frames' bytes (one lane per frame), device = read(decoder='device')
+            (vtf_jpeg_decode_split).  ms per det-batch, the ratios, the device leg's two kernel
+            stages by HIP events and a seg_bytes sweep (64, 128, 256, 512).
 
 The CPU legs are the oracle (ViT torch-CPU restatement) and sklearn 1.7.2 itself (the
 reference's own grouping dependency), on bounded samples, timed on this host's cores.
@@ -42,6 +49,7 @@ reference's own grouping dependency), on bounded samples, timed on this host's c
   python scripts/bench_stages.py resize [--steps 20] [--warmup 3]
   python scripts/bench_stages.py jpeg_decode [--steps 10] [--warmup 3]
   python scripts/bench_stages.py handoff [--steps 10] [--warmup 3]
+  python scripts/bench_stages.py mjpeg --steps 20 --warmup 3
 """
 import argparse
 import json
@@ -596,9 +604,88 @@ def bench_handoff(a):
     print(json.dumps(res), flush=True)
 
 
+def bench_mjpeg(a):
+    import io
+    import tempfile
+    from PIL import Image
+    from videotofaces import _native as nat
+    from videotofaces import synth
+    from videotofaces.utils import jpeg_decode
+    from videotofaces.video import MJPEGReader, write_mjpeg_avi
+    dev = torch.device('cuda:0')
+    B, H, W, quality = 16, 720, 1280, 90
+    frames = synth.make_frames_device(0, B, H, W, seed=0, device=dev, style='blobs').cpu().numpy()
+    jpegs = []
+    for f in frames:
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(f[:, :, ::-1])).save(buf, 'JPEG', quality=quality)
+        jpegs.append(buf.getvalue())
+    idx = list(range(B))
+    stage_ms = np.zeros(2, np.float32)
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize(dev)
+        ts = []
+        for _ in range(a.steps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return ts
+
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, 'clip.avi')
+        write_mjpeg_avi(path, jpegs, fps='25:1')
+        r = MJPEGReader(path)
+        # the three legs give the same frames
+        want = r.read(idx, dev, 'host')
+        assert torch.equal(r.read(idx, dev, 'device'), want)
+        atlas, sizes, status = jpeg_decode([r.frame_bytes(i) for i in idx], dev)
+        assert not status.any() and torch.equal(atlas, want)
+        del atlas, want
+        out = {'host': timed(lambda: r.read(idx, dev, 'host')),
+               'serial': timed(lambda: jpeg_decode([r.frame_bytes(i) for i in idx], dev)),
+               'device': timed(lambda: r.read(idx, dev, 'device'))}
+        nat.check(nat.lib().vtf_jpeg_decode_profile(1, None))
+        stages = []
+        for _ in range(a.steps):
+            r.read(idx, dev, 'device')
+            nat.check(nat.lib().vtf_jpeg_decode_profile(1, stage_ms.ctypes.data))
+            stages.append(stage_ms.copy())
+        sweep = {}
+        for seg in (64, 128, 256, 512):
+            ts, st = timed(lambda: r.read(idx, dev, 'device', seg)), []
+            for _ in range(a.steps):
+                r.read(idx, dev, 'device', seg)
+                nat.check(nat.lib().vtf_jpeg_decode_profile(1, stage_ms.ctypes.data))
+                st.append(float(stage_ms[0]))
+            sweep[str(seg)] = {'read_ms': round(float(np.median(ts)), 3), 'stage1_ms': round(float(np.median(st)), 3)}
+        nat.check(nat.lib().vtf_jpeg_decode_profile(0, None))
+        r.close()
+    med = {k: float(np.median(v)) for k, v in out.items()}
+    stages = np.median(np.array(stages), axis=0)
+    res = {'metric': 'Motion-JPEG det-batch read, ms per 16 frames of 720p (Pillow quality 90) up to BGR frames in HBM',
+           'value': round(med['device'], 3), 'unit': 'ms', 'higher_is_better': False, 'n_gpus': 1,
+           'steps': a.steps, 'warmup': a.warmup, 'data': 'synthetic (device-generated blobs frames, Pillow-encoded)',
+           'config': {'frames': B, 'height': H, 'width': W, 'quality': quality,
+                      'file_bytes': sum(len(j) for j in jpegs), 'host_reader': 'Pillow open().convert(RGB)',
+                      'host_cores_used': 1},
+           'host_ms': round(med['host'], 3), 'host_ms_min': round(min(out['host']), 3),
+           'serial_ms': round(med['serial'], 3), 'serial_ms_min': round(min(out['serial']), 3),
+           'device_ms': round(med['device'], 3), 'device_ms_min': round(min(out['device']), 3),
+           'device_stage1_entropy_ms': round(float(stages[0]), 3),
+           'device_stage2_pixels_ms': round(float(stages[1]), 3),
+           'host_over_device': round(med['host'] / med['device'], 2),
+           'serial_over_device': round(med['serial'] / med['device'], 2),
+           'seg_bytes_sweep': sweep}
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg', 'resize', 'jpeg_decode', 'handoff'])
+    ap.add_argument('stage', choices=['vit', 'grouping', 'jpeg', 'resize', 'jpeg_decode', 'handoff', 'mjpeg'])
     ap.add_argument('--vit-model', default='vit_l', choices=['vit_b', 'vit_l'])
     ap.add_argument('--vit-precision', default='f16x', choices=['fp32', 'f16x'])
     ap.add_argument('--enc-batch', type=int, default=128)
@@ -612,7 +699,7 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     a = ap.parse_args()
     {'vit': bench_vit, 'grouping': bench_grouping, 'jpeg': bench_jpeg, 'resize': bench_resize,
-     'jpeg_decode': bench_jpeg_decode, 'handoff': bench_handoff}[a.stage](a)
+     'jpeg_decode': bench_jpeg_decode, 'handoff': bench_handoff, 'mjpeg': bench_mjpeg}[a.stage](a)
 
 
 if __name__ == '__main__':

@@ -19,7 +19,8 @@
 //                   columns < w are written.  A file whose column pass leaves the int16 range (no
 //                   8-bit image does) is marked corrupt: host fallback.
 // One H2D copy of the bytes, one of the tables; one sync at the end (two with a corrupt file, whose
-// slot is then zero-filled).
+// slot is then zero-filled).  jpeg_decode_call is the host side of a call; vtf_jpeg_decode_split
+// (jpeg_decode_split.hip) runs it with another stage 1, made for long scans.
 //
 // vtf_faces_to_atlas (k_faces_to_atlas) fills such slots from faces that are in HBM already: the
 // decoded pixels vtf_jpeg_encode_crops_decoded left there.
@@ -30,6 +31,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "jpeg_decode.hpp"
 #include "jpeg_entropy.hpp"
 #include "jpeg_parse.hpp"
 #include "jpeg_recon.hpp"
@@ -41,16 +43,6 @@ namespace {
 using jpg::HuffSet;
 
 constexpr int FILES_PER_WG = 4;  // one wave each
-
-// one decodable file of a call
-struct DecFile {
-    int64_t scan_begin, scan_end;  // in the uploaded bytes
-    int32_t h, w;
-    int32_t mw;    // MCUs per row
-    int32_t set;   // index of its HuffSet
-    int32_t slot;  // its index among the call's N files
-    int32_t pad;
-};
 
 // ---------------------------------------------------------------------------------- stage 1
 __global__ __launch_bounds__(64 * FILES_PER_WG) void k_jpeg_entropy(const uint8_t* __restrict__ data,
@@ -126,6 +118,147 @@ struct Events {
 
 }  // namespace
 
+void jpeg_decode_call(const uint8_t* data, const int64_t* offsets, int64_t N, uint8_t* d_bgr, int Hmax, int Wmax,
+                      int64_t frame_stride, int64_t row_stride, int32_t* out_sizes, int32_t* out_status, int seg_bytes,
+                      hipStream_t st) {
+    VTF_CHECK(N >= 0, VTF_E_ARG, "bad argument");
+    if (N == 0) return;
+    VTF_CHECK(data && offsets && out_sizes && out_status, VTF_E_ARG, "null argument");
+    VTF_CHECK(N < (1 << 24), VTF_E_LIMIT, "jpeg: too many files in one call");
+    VTF_CHECK(offsets[0] >= 0, VTF_E_ARG, "jpeg: negative offset");
+    for (int64_t i = 0; i < N; i++)
+        VTF_CHECK(offsets[i + 1] >= offsets[i], VTF_E_ARG, "jpeg: offsets must not decrease");
+    VTF_CHECK(Hmax >= 0 && Wmax >= 0 && row_stride >= (int64_t)Wmax * 3 &&
+                  (Hmax == 0 || frame_stride >= (int64_t)(Hmax - 1) * row_stride + (int64_t)Wmax * 3),
+              VTF_E_ARG, "jpeg: strides too small for Hmax x Wmax");
+    VTF_CHECK(d_bgr || Hmax == 0 || Wmax == 0, VTF_E_ARG, "null argument");
+
+    // classify on the host; de-duplicate the Huffman table sets
+    const int64_t base = offsets[0], nbytes = offsets[N] - base;
+    std::vector<DecFile> files;
+    std::vector<int32_t> mcu0(1, 0);
+    std::vector<uint16_t> quant;
+    std::vector<HuffSet> sets;
+    std::map<std::string, int> set_of;
+    std::vector<int64_t> corrupt;
+    int64_t mcus = 0;
+    jpg::Parsed P;
+    for (int64_t i = 0; i < N; i++) {
+        jpg::parse(data + offsets[i], offsets[i + 1] - offsets[i], P);
+        out_sizes[2 * i] = P.h, out_sizes[2 * i + 1] = P.w;
+        if (P.kind == jpg::KIND_INVALID) {
+            out_sizes[2 * i] = out_sizes[2 * i + 1] = 0;
+            out_status[i] = jpg::ST_CORRUPT;
+            corrupt.push_back(i);
+            continue;
+        }
+        if (P.kind == jpg::KIND_UNSUPPORTED) {
+            out_status[i] = jpg::ST_UNSUPPORTED;
+            continue;
+        }
+        if (P.h > Hmax || P.w > Wmax) {
+            out_status[i] = jpg::ST_TOO_LARGE;
+            continue;
+        }
+        out_status[i] = jpg::ST_OK;
+        std::string key;
+        for (int c = 0; c < 3; c++)
+            for (const jpg::HuffSpec* t : {&P.dc[c], &P.ac[c]}) {
+                key.append((const char*)t->bits, 16);
+                key.append((const char*)t->vals, (size_t)t->n);
+            }
+        auto it = set_of.find(key);
+        if (it == set_of.end()) {
+            it = set_of.emplace(key, (int)sets.size()).first;
+            sets.emplace_back();
+            for (int c = 0; c < 3; c++) {
+                jpg::build_huff(P.dc[c].bits, P.dc[c].vals, P.dc[c].n, sets.back().dc[c]);
+                jpg::build_huff(P.ac[c].bits, P.ac[c].vals, P.ac[c].n, sets.back().ac[c]);
+            }
+        }
+        DecFile d;
+        d.scan_begin = offsets[i] - base + P.scan_begin, d.scan_end = offsets[i] - base + P.scan_end;
+        d.h = P.h, d.w = P.w, d.mw = (P.w + 15) >> 4;
+        d.set = it->second, d.slot = (int32_t)i, d.pad = 0;
+        files.push_back(d);
+        mcus += (int64_t)d.mw * ((P.h + 15) >> 4);
+        VTF_CHECK(mcus < ((int64_t)1 << 31) / 384, VTF_E_LIMIT, "jpeg: too many pixels in one call");
+        mcu0.push_back((int32_t)mcus);
+        quant.insert(quant.end(), &P.q[0][0], &P.q[0][0] + 192);
+    }
+    const int M = (int)files.size();
+    if (M > 0) {
+        StreamScratch sc = stream_scratch(st);
+        Arena& ar = *sc.ar;
+        // tables: files, first MCUs, quantisers, Huffman sets -> one pinned block, one copy
+        auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        const size_t files_at = 0, mcu0_at = up16(files_at + (size_t)M * sizeof(DecFile));
+        const size_t quant_at = up16(mcu0_at + ((size_t)M + 1) * 4);
+        const size_t sets_at = up16(quant_at + (size_t)M * 192 * 2);
+        const size_t recon_at = up16(sets_at + sets.size() * sizeof(HuffSet));
+        const size_t up_b = recon_at + (size_t)M * sizeof(ReconImage);
+        Arena::Mail up = ar.mail(0, up_b);
+        uint8_t* h_up = (uint8_t*)up.h;
+        std::memcpy(h_up + files_at, files.data(), (size_t)M * sizeof(DecFile));
+        std::memcpy(h_up + mcu0_at, mcu0.data(), ((size_t)M + 1) * 4);
+        std::memcpy(h_up + quant_at, quant.data(), (size_t)M * 192 * 2);
+        std::memcpy(h_up + sets_at, sets.data(), sets.size() * sizeof(HuffSet));
+        ReconImage* h_recon = (ReconImage*)(h_up + recon_at);
+        for (int f = 0; f < M; f++)  // file f's own quantisers, slot `slot` of the atlas
+            h_recon[f] = ReconImage{files[f].h, files[f].w, files[f].mw, f, (int64_t)files[f].slot * frame_stride,
+                                    row_stride};
+        uint8_t* d_up = (uint8_t*)ar.get(0, up_b);
+        VTF_HIP(hipMemcpyAsync(d_up, up.h, up_b, hipMemcpyHostToDevice, st));
+        const DecFile* d_files = (const DecFile*)(d_up + files_at);
+        const int32_t* d_mcu0 = (const int32_t*)(d_up + mcu0_at);
+        const uint16_t* d_quant = (const uint16_t*)(d_up + quant_at);
+        const HuffSet* d_sets = (const HuffSet*)(d_up + sets_at);
+        const ReconImage* d_recon = (const ReconImage*)(d_up + recon_at);
+
+        uint8_t* d_data = ar.get<uint8_t>(1, (size_t)nbytes);
+        VTF_HIP(hipMemcpyAsync(d_data, data + base, (size_t)nbytes, hipMemcpyHostToDevice, st));
+        int16_t* coef = ar.get<int16_t>(2, (size_t)mcus * 384);
+        uint8_t* yplane = ar.get<uint8_t>(3, (size_t)mcus * 256);
+        uint8_t* cplane = ar.get<uint8_t>(4, (size_t)mcus * 128);
+        int32_t* d_status = ar.get<int32_t>(5, (size_t)M);
+        std::vector<int32_t> h_status((size_t)M, jpg::ST_CORRUPT);
+
+        Events ev;
+        if (g_profile)
+            for (hipEvent_t& e : ev.e) VTF_HIP(hipEventCreate(&e));
+        VTF_HIP(hipMemsetAsync(coef, 0, (size_t)mcus * 384 * 2, st));
+        if (g_profile) VTF_HIP(hipEventRecord(ev.e[0], st));
+        if (seg_bytes < 0)
+            k_jpeg_entropy<<<cdiv(M, FILES_PER_WG), 64 * FILES_PER_WG, 0, st>>>(d_data, d_files, d_mcu0, M, d_sets, coef,
+                                                                                d_status);
+        else
+            launch_entropy_split(ar, d_data, nbytes, files.data(), d_files, d_mcu0, M, d_sets, coef, d_status, seg_bytes,
+                                 st);
+        if (g_profile) VTF_HIP(hipEventRecord(ev.e[1], st));
+        launch_recon(d_recon, d_mcu0, M, mcus, d_quant, coef, d_status, yplane, cplane, d_bgr, st);
+        if (g_profile) VTF_HIP(hipEventRecord(ev.e[2], st));
+        VTF_HIP(hipGetLastError());
+        VTF_HIP(hipMemcpyAsync(h_status.data(), d_status, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+        VTF_HIP(hipStreamSynchronize(st));
+        if (g_profile) {
+            VTF_HIP(hipEventElapsedTime(&g_stage_ms[0], ev.e[0], ev.e[1]));
+            VTF_HIP(hipEventElapsedTime(&g_stage_ms[1], ev.e[1], ev.e[2]));
+        }
+        for (int f = 0; f < M; f++)
+            if (h_status[f] != jpg::ST_OK) {
+                out_status[files[f].slot] = jpg::ST_CORRUPT;
+                corrupt.push_back(files[f].slot);
+            }
+    }
+    // a corrupt file's slot is zero-filled
+    if (!corrupt.empty() && Hmax > 0 && Wmax > 0) {
+        for (int64_t i : corrupt)
+            VTF_HIP(hipMemset2DAsync(d_bgr + i * frame_stride, (size_t)row_stride, 0, (size_t)Wmax * 3, (size_t)Hmax,
+                                     st));
+        VTF_HIP(hipStreamSynchronize(st));
+    }
+}
+
 }  // namespace vtf
 
 using namespace vtf;
@@ -152,139 +285,8 @@ extern "C" int vtf_jpeg_decode(const uint8_t* data, const int64_t* offsets, int6
                                int Wmax, int64_t frame_stride, int64_t row_stride, int32_t* out_sizes,
                                int32_t* out_status, void* hip_stream) {
     return guarded_on(stream_device((hipStream_t)hip_stream), [&] {
-        VTF_CHECK(N >= 0, VTF_E_ARG, "bad argument");
-        if (N == 0) return;
-        VTF_CHECK(data && offsets && out_sizes && out_status, VTF_E_ARG, "null argument");
-        VTF_CHECK(N < (1 << 24), VTF_E_LIMIT, "jpeg: too many files in one call");
-        VTF_CHECK(offsets[0] >= 0, VTF_E_ARG, "jpeg: negative offset");
-        for (int64_t i = 0; i < N; i++)
-            VTF_CHECK(offsets[i + 1] >= offsets[i], VTF_E_ARG, "jpeg: offsets must not decrease");
-        VTF_CHECK(Hmax >= 0 && Wmax >= 0 && row_stride >= (int64_t)Wmax * 3 &&
-                      (Hmax == 0 || frame_stride >= (int64_t)(Hmax - 1) * row_stride + (int64_t)Wmax * 3),
-                  VTF_E_ARG, "jpeg: strides too small for Hmax x Wmax");
-        VTF_CHECK(d_bgr || Hmax == 0 || Wmax == 0, VTF_E_ARG, "null argument");
-        hipStream_t st = (hipStream_t)hip_stream;
-
-        // classify on the host; de-duplicate the Huffman table sets
-        const int64_t base = offsets[0], nbytes = offsets[N] - base;
-        std::vector<DecFile> files;
-        std::vector<int32_t> mcu0(1, 0);
-        std::vector<uint16_t> quant;
-        std::vector<HuffSet> sets;
-        std::map<std::string, int> set_of;
-        std::vector<int64_t> corrupt;
-        int64_t mcus = 0;
-        jpg::Parsed P;
-        for (int64_t i = 0; i < N; i++) {
-            jpg::parse(data + offsets[i], offsets[i + 1] - offsets[i], P);
-            out_sizes[2 * i] = P.h, out_sizes[2 * i + 1] = P.w;
-            if (P.kind == jpg::KIND_INVALID) {
-                out_sizes[2 * i] = out_sizes[2 * i + 1] = 0;
-                out_status[i] = jpg::ST_CORRUPT;
-                corrupt.push_back(i);
-                continue;
-            }
-            if (P.kind == jpg::KIND_UNSUPPORTED) {
-                out_status[i] = jpg::ST_UNSUPPORTED;
-                continue;
-            }
-            if (P.h > Hmax || P.w > Wmax) {
-                out_status[i] = jpg::ST_TOO_LARGE;
-                continue;
-            }
-            out_status[i] = jpg::ST_OK;
-            std::string key;
-            for (int c = 0; c < 3; c++)
-                for (const jpg::HuffSpec* t : {&P.dc[c], &P.ac[c]}) {
-                    key.append((const char*)t->bits, 16);
-                    key.append((const char*)t->vals, (size_t)t->n);
-                }
-            auto it = set_of.find(key);
-            if (it == set_of.end()) {
-                it = set_of.emplace(key, (int)sets.size()).first;
-                sets.emplace_back();
-                for (int c = 0; c < 3; c++) {
-                    jpg::build_huff(P.dc[c].bits, P.dc[c].vals, P.dc[c].n, sets.back().dc[c]);
-                    jpg::build_huff(P.ac[c].bits, P.ac[c].vals, P.ac[c].n, sets.back().ac[c]);
-                }
-            }
-            DecFile d;
-            d.scan_begin = offsets[i] - base + P.scan_begin, d.scan_end = offsets[i] - base + P.scan_end;
-            d.h = P.h, d.w = P.w, d.mw = (P.w + 15) >> 4;
-            d.set = it->second, d.slot = (int32_t)i, d.pad = 0;
-            files.push_back(d);
-            mcus += (int64_t)d.mw * ((P.h + 15) >> 4);
-            VTF_CHECK(mcus < ((int64_t)1 << 31) / 384, VTF_E_LIMIT, "jpeg: too many pixels in one call");
-            mcu0.push_back((int32_t)mcus);
-            quant.insert(quant.end(), &P.q[0][0], &P.q[0][0] + 192);
-        }
-        const int M = (int)files.size();
-        if (M > 0) {
-            StreamScratch sc = stream_scratch(st);
-            Arena& ar = *sc.ar;
-            // tables: files, first MCUs, quantisers, Huffman sets -> one pinned block, one copy
-            auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-            const size_t files_at = 0, mcu0_at = up16(files_at + (size_t)M * sizeof(DecFile));
-            const size_t quant_at = up16(mcu0_at + ((size_t)M + 1) * 4);
-            const size_t sets_at = up16(quant_at + (size_t)M * 192 * 2);
-            const size_t recon_at = up16(sets_at + sets.size() * sizeof(HuffSet));
-            const size_t up_b = recon_at + (size_t)M * sizeof(ReconImage);
-            Arena::Mail up = ar.mail(0, up_b);
-            uint8_t* h_up = (uint8_t*)up.h;
-            std::memcpy(h_up + files_at, files.data(), (size_t)M * sizeof(DecFile));
-            std::memcpy(h_up + mcu0_at, mcu0.data(), ((size_t)M + 1) * 4);
-            std::memcpy(h_up + quant_at, quant.data(), (size_t)M * 192 * 2);
-            std::memcpy(h_up + sets_at, sets.data(), sets.size() * sizeof(HuffSet));
-            ReconImage* h_recon = (ReconImage*)(h_up + recon_at);
-            for (int f = 0; f < M; f++)  // file f's own quantisers, slot `slot` of the atlas
-                h_recon[f] = ReconImage{files[f].h, files[f].w, files[f].mw, f, (int64_t)files[f].slot * frame_stride,
-                                        row_stride};
-            uint8_t* d_up = (uint8_t*)ar.get(0, up_b);
-            VTF_HIP(hipMemcpyAsync(d_up, up.h, up_b, hipMemcpyHostToDevice, st));
-            const DecFile* d_files = (const DecFile*)(d_up + files_at);
-            const int32_t* d_mcu0 = (const int32_t*)(d_up + mcu0_at);
-            const uint16_t* d_quant = (const uint16_t*)(d_up + quant_at);
-            const HuffSet* d_sets = (const HuffSet*)(d_up + sets_at);
-            const ReconImage* d_recon = (const ReconImage*)(d_up + recon_at);
-
-            uint8_t* d_data = ar.get<uint8_t>(1, (size_t)nbytes);
-            VTF_HIP(hipMemcpyAsync(d_data, data + base, (size_t)nbytes, hipMemcpyHostToDevice, st));
-            int16_t* coef = ar.get<int16_t>(2, (size_t)mcus * 384);
-            uint8_t* yplane = ar.get<uint8_t>(3, (size_t)mcus * 256);
-            uint8_t* cplane = ar.get<uint8_t>(4, (size_t)mcus * 128);
-            int32_t* d_status = ar.get<int32_t>(5, (size_t)M);
-            std::vector<int32_t> h_status((size_t)M, jpg::ST_CORRUPT);
-
-            Events ev;
-            if (g_profile)
-                for (hipEvent_t& e : ev.e) VTF_HIP(hipEventCreate(&e));
-            VTF_HIP(hipMemsetAsync(coef, 0, (size_t)mcus * 384 * 2, st));
-            if (g_profile) VTF_HIP(hipEventRecord(ev.e[0], st));
-            k_jpeg_entropy<<<cdiv(M, FILES_PER_WG), 64 * FILES_PER_WG, 0, st>>>(d_data, d_files, d_mcu0, M, d_sets, coef,
-                                                                                d_status);
-            if (g_profile) VTF_HIP(hipEventRecord(ev.e[1], st));
-            launch_recon(d_recon, d_mcu0, M, mcus, d_quant, coef, d_status, yplane, cplane, d_bgr, st);
-            if (g_profile) VTF_HIP(hipEventRecord(ev.e[2], st));
-            VTF_HIP(hipGetLastError());
-            VTF_HIP(hipMemcpyAsync(h_status.data(), d_status, (size_t)M * 4, hipMemcpyDeviceToHost, st));
-            VTF_HIP(hipStreamSynchronize(st));
-            if (g_profile) {
-                VTF_HIP(hipEventElapsedTime(&g_stage_ms[0], ev.e[0], ev.e[1]));
-                VTF_HIP(hipEventElapsedTime(&g_stage_ms[1], ev.e[1], ev.e[2]));
-            }
-            for (int f = 0; f < M; f++)
-                if (h_status[f] != jpg::ST_OK) {
-                    out_status[files[f].slot] = jpg::ST_CORRUPT;
-                    corrupt.push_back(files[f].slot);
-                }
-        }
-        // a corrupt file's slot is zero-filled
-        if (!corrupt.empty() && Hmax > 0 && Wmax > 0) {
-            for (int64_t i : corrupt)
-                VTF_HIP(hipMemset2DAsync(d_bgr + i * frame_stride, (size_t)row_stride, 0, (size_t)Wmax * 3, (size_t)Hmax,
-                                         st));
-            VTF_HIP(hipStreamSynchronize(st));
-        }
+        jpeg_decode_call(data, offsets, N, d_bgr, Hmax, Wmax, frame_stride, row_stride, out_sizes, out_status, -1,
+                         (hipStream_t)hip_stream);
     });
 }
 

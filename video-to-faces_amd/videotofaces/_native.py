@@ -93,6 +93,7 @@ SIGNATURES = {
     'vtf_resize_crops': [_p, _i32, _i32, _i32, _i64, _i64, _p, _p, _i64, _p, _i32, _i32, _i64, _i64, _p],
     'vtf_jpeg_probe': [_p, _i64, _p],
     'vtf_jpeg_decode': [_p, _p, _i64, _p, _i32, _i32, _i64, _i64, _p, _p, _p],
+    'vtf_jpeg_decode_split': [_p, _p, _i64, _p, _i32, _i32, _i64, _i64, _p, _p, _i32, _p],
     'vtf_jpeg_decode_profile': [_i32, _p],
     'vtf_yuv_to_bgr': [_p, _i64, _i32, _i32, _i32, _i32, _i64, _p, _i64, _i64, _p],
     'vtf_rcnn_create': [_p, _i64, _i32, _i32, _p],

@@ -120,12 +120,19 @@ def detect_crops(model, frames_dev, frame_offset=0, mscore=0.4, msize=50, mborde
 
 
 # ------------------------------------------------------------------ detection stage (detection.py:32-158)
-def frame_source(path, video_reader='opencv', device=None):
+MJPEG_EXTS = ('.avi', '.mjpeg', '.mjpg')
+
+
+def frame_source(path, video_reader='opencv', device=None, mjpeg_reader='auto'):
     """(n_frames, fps, read(indices) -> uint8 [B,H,W,3] BGR) for a video file (OpenCV, as
     detection.py:82-111), a YUV4MPEG2 stream (.y4m: decoded frames converted on the GPU, read()
     returns them in HBM of `device`, videotofaces/video.py), a .npy file of frames, or an
-    in-memory uint8 array (fps 1)."""
+    in-memory uint8 array (fps 1).  mjpeg_reader: 'device' / 'host' read .avi, .mjpeg and .mjpg
+    files as Motion-JPEG with video.MJPEGReader and that decoder (frames in HBM, libjpeg's pixels);
+    'auto' does so, on the device, only where OpenCV is not installed."""
     import numpy as np
+    if mjpeg_reader not in ('auto', 'device', 'host'):
+        raise ValueError("mjpeg_reader must be 'auto', 'device' or 'host'")
     if isinstance(path, np.ndarray):
         arr = path
         return arr.shape[0], 1, lambda idx: arr[idx]
@@ -136,11 +143,22 @@ def frame_source(path, video_reader='opencv', device=None):
         from .video import Y4MReader
         r = Y4MReader(path)
         return r.n_frames, r.fps, lambda idx: r.read(idx, device)
-    try:
-        import cv2
-    except ImportError:
+    is_mjpeg = str(path).lower().endswith(MJPEG_EXTS)
+    cv2 = None
+    if not (is_mjpeg and mjpeg_reader != 'auto'):
+        try:
+            import cv2
+        except ImportError:
+            pass
+    if cv2 is None:
+        if is_mjpeg:
+            from .video import MJPEGReader
+            r = MJPEGReader(path)
+            decoder = 'device' if mjpeg_reader == 'auto' else mjpeg_reader
+            return r.n_frames, r.fps, lambda idx: r.read(idx, device, decoder)
         raise RuntimeError('decoding %s needs OpenCV (cv2), which is not installed; pass frames as a .npy file or '
-                           'a uint8 array [F,H,W,3] instead' % path)
+                           'a uint8 array [F,H,W,3] instead.  Motion-JPEG files (.avi, .mjpeg, .mjpg) are read '
+                           'without it' % path)
     cap = cv2.VideoCapture(path)
     n, fps = round(cap.get(cv2.CAP_PROP_FRAME_COUNT)), round(cap.get(cv2.CAP_PROP_FPS))
     state = {'c': 0}
@@ -312,7 +330,7 @@ def detect_faces(files, model, vid_params, det_params, save_params, hash_thr, jp
     import numpy as np
     from .dupes import remove_dupes_overall, unpack_hash
     from . import _native as nat
-    video_step, video_fragment, video_area, video_reader = vid_params
+    video_step, video_fragment, video_area, video_reader, mjpeg_reader = vid_params
     bs = det_params[0]
     out_dir, out_prefix = save_params[0], save_params[1]
     os.makedirs(osp.join(out_dir, 'faces'), exist_ok=True)
@@ -322,7 +340,7 @@ def detect_faces(files, model, vid_params, det_params, save_params, hash_thr, jp
     for k, f in enumerate(files):
         print('Processing ' + (f if isinstance(f, str) else 'in-memory frames'))
         sp = (out_dir, out_prefix + ('' if len(files) == 1 else '%02d_' % (k + 1)), *save_params[2:])
-        n, fps, read = frame_source(f, video_reader, nat.device_of(model))
+        n, fps, read = frame_source(f, video_reader, nat.device_of(model), mjpeg_reader)
         step = max(1, round(fps * video_step))
         bgn = step if not video_fragment or video_fragment[0] < 0 else max(step, round(60 * video_fragment[0] * fps))
         end = n if not video_fragment or video_fragment[1] < 0 else min(n, round(60 * video_fragment[1] * fps + 1))

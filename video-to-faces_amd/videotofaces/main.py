@@ -31,7 +31,15 @@ and every all-pairs / K-means pass runs in libvtf_hip.so.  Additions, all opt-in
     (vtf_faces_to_atlas) without opening a file.  The files are written as always; 'files'
     (default) reads them back as jpeg_decoder says.  What does not fit the store's budget
     (facestore.HANDOFF_BYTES) goes by file.  Other modes
-    ignore it; the multi-process path (parallel.py) does not use it.
+    ignore it; the multi-process path (parallel.py) does not use it;
+  * mjpeg_reader reads Motion-JPEG video (.avi with an MJPG stream, .mjpeg, .mjpg) without
+    OpenCV: video.MJPEGReader indexes the frames of the memory-mapped file and decodes the sampled
+    ones on the GPU (vtf_jpeg_decode_split: one workgroup per frame, a lane per segment of its
+    scan), frames the device does not decode with Pillow; the frames reach the detector in HBM.
+    'auto' (default) leaves such files to OpenCV where it is installed and reads them this way
+    where it is not; 'device' / 'host' always read them this way, decoding on the GPU / with
+    Pillow.  The pixels are libjpeg's (Pillow's); OpenCV decodes MJPEG through FFmpeg, whose
+    pixels can differ in low bits.
 """
 import os.path as osp
 
@@ -79,7 +87,7 @@ def video_to_faces(input_path=None, input_ext=None,
                    enc_dup_thr=0.25, enc_oth_thr=0.9,
                    _test_enc=False, _test_exclude_other=False,
                    decoupled=False, det_precision='fp32', enc_precision='fp32', jpeg_encoder='host',
-                   jpeg_decoder='host', face_handoff='files'):
+                   jpeg_decoder='host', face_handoff='files', mjpeg_reader='auto'):
     from .detection import detect_faces
     from .dupes import remove_dupes_overall
     from .grouping import encode_faces, cluster_faces, classify_faces
@@ -91,6 +99,8 @@ def video_to_faces(input_path=None, input_ext=None,
     if not prep._one_of(jpeg_decoder, 'jpeg_decoder', ['host', 'device']):
         return
     if not prep._one_of(face_handoff, 'face_handoff', ['files', 'device']):
+        return
+    if not prep._one_of(mjpeg_reader, 'mjpeg_reader', ['auto', 'device', 'host']):
         return
     if mode == 'full' and face_handoff == 'device' and jpeg_encoder != 'device':
         print('ERROR: face_handoff="device" needs jpeg_encoder="device"')
@@ -129,7 +139,7 @@ def video_to_faces(input_path=None, input_ext=None,
         files = [input_path] if in_memory else prep.get_video_list(input_path, input_ext)
         if not len(files):
             return
-        vid_params = (video_step, video_fragment, video_area, video_reader)
+        vid_params = (video_step, video_fragment, video_area, video_reader, mjpeg_reader)
         det_params = (det_batch_size, det_min_score, det_min_size, det_min_border, det_scale, det_square)
         save_params = (out_dir, out_prefix, resize_to, save_frames, save_rejects, save_dupes)
         detector = get_detector(style, det_model, device, det_precision)

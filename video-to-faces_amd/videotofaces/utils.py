@@ -239,7 +239,7 @@ def jpeg_probe(data):
     return int(info[0]), int(info[1]), int(info[2])
 
 
-def jpeg_decode(files, device=None, probed=None, min_size=(1, 1)):
+def jpeg_decode(files, device=None, probed=None, min_size=(1, 1), scan='serial', seg_bytes=0):
     """cv2.imread of every file (a list of `bytes`, each a whole JPEG file) on the device
     (vtf_jpeg_decode) -> (atlas, sizes, status): a CUDA uint8 BGR tensor [N,Hmax,Wmax,3] with file
     i in atlas[i, :h, :w] (the rest of a slot is not written), np.int32 [N,2] (h, w) and np.int32
@@ -248,10 +248,16 @@ def jpeg_decode(files, device=None, probed=None, min_size=(1, 1)):
     from the probed headers).  The pixels are libjpeg's, bit for bit.  The headers are probed on
     the host to size the atlas; then one library call and one H2D copy of the compressed bytes.
     probed: jpeg_probe's (h, w, kind) of every file when the caller has them already.  min_size:
-    (Hmax, Wmax) is at least this, for slots the caller fills itself (files with status != 0)."""
+    (Hmax, Wmax) is at least this, for slots the caller fills itself (files with status != 0).
+    scan: 'serial' decodes a file's scan with one lane (many small files per call: face crops),
+    'split' with the lanes of a workgroup, each on a segment of seg_bytes of the scan
+    (vtf_jpeg_decode_split: large files, video frames; seg_bytes 0 = the library's default,
+    otherwise a multiple of 4 in [4, 4096]).  The same atlas, sizes and statuses either way."""
     import numpy as np
     import torch
     from . import _native as nat
+    if scan not in ('serial', 'split'):
+        raise ValueError("scan must be 'serial' or 'split'")
     dev = nat.require_gpu(device)
     n = len(files)
     sizes, status = np.zeros((n, 2), np.int32), np.zeros(n, np.int32)
@@ -268,7 +274,10 @@ def jpeg_decode(files, device=None, probed=None, min_size=(1, 1)):
     np.cumsum([len(f) for f in files], out=offs[1:])
     data = np.frombuffer(b''.join(files) or b'\0', np.uint8)
     with torch.cuda.device(dev):
-        nat.check(nat.lib().vtf_jpeg_decode(data.ctypes.data, offs.ctypes.data, n, nat.ptr(atlas), hm, wm,
-                                            atlas.stride(0), atlas.stride(1), sizes.ctypes.data, status.ctypes.data,
-                                            nat.stream_ptr(dev)))
+        args = (data.ctypes.data, offs.ctypes.data, n, nat.ptr(atlas), hm, wm, atlas.stride(0), atlas.stride(1),
+                sizes.ctypes.data, status.ctypes.data)
+        if scan == 'split':
+            nat.check(nat.lib().vtf_jpeg_decode_split(*args, int(seg_bytes), nat.stream_ptr(dev)))
+        else:
+            nat.check(nat.lib().vtf_jpeg_decode(*args, nat.stream_ptr(dev)))
     return atlas, sizes, status

@@ -8,11 +8,18 @@ memory-mapped, the sampled frames' planes are gathered into pinned host memory a
 the file (1.5 bytes per 4:2:0 pixel over PCIe, not 3) and one launch of vtf_yuv_to_bgr turns
 them into the BGR frames in HBM that the detectors read in place.
 
+Motion-JPEG is the one compressed format that needs no codec this image lacks: its frames are
+baseline JPEG files, which the library decodes on the device.  MJPEGReader reads it from AVI files
+and from raw .mjpeg streams (`ffmpeg -i in.mp4 -c:v mjpeg out.avi`, `-f mjpeg out.mjpeg`): the
+file is memory-mapped, the frames are indexed once, and read() sends the compressed bytes of the
+sampled frames to vtf_jpeg_decode_split, which writes the BGR frames in HBM.
+
 YUV4MPEG2: a header line 'YUV4MPEG2 W<w> H<h> F<num>:<den> [I..] [A..] [C<chroma>] [X..]\\n',
 then per frame 'FRAME[ params]\\n' + Y [H][W] + U, V planes (4:2:0: ceil(W/2) x ceil(H/2)).
 """
 import mmap
 import os
+import struct
 
 import numpy as np
 
@@ -148,3 +155,308 @@ def yuv_to_bgr(planes, height, width, chroma=420, full_range=False, device=None)
     nat.check(nat.lib().vtf_yuv_to_bgr(nat.ptr(t), t.shape[0], height, width, chroma, int(bool(full_range)),
                                        t.stride(0), nat.ptr(out), out.stride(0), out.stride(1), nat.stream_ptr(dev)))
     return out
+
+
+# ------------------------------------------------------------------------------------ Motion-JPEG
+def _jpeg_walk(buf, p, size):
+    """One JPEG file starting at buf[p] (SOI), walked by its marker segments' lengths ->
+    (end, h, w): end = the offset after its EOI, or -1 when the bytes end first or are no JPEG;
+    (h, w) from the first frame header (0, 0 when there is none).  Inside a scan the next marker
+    is an FF followed by neither 00 nor a restart marker (D0-D7) nor another FF (fill): an FF D9
+    inside a segment, such as an EXIF thumbnail's, is never looked at."""
+    if p + 4 > size or buf[p] != 0xFF or buf[p + 1] != 0xD8:
+        return -1, 0, 0
+    p += 2
+    h = w = 0
+    while True:
+        if p + 2 > size or buf[p] != 0xFF:
+            return -1, h, w
+        while p < size and buf[p] == 0xFF:  # fill bytes
+            p += 1
+        if p >= size:
+            return -1, h, w
+        m = buf[p]
+        p += 1
+        if m == 0xD9:
+            return p, h, w
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0x00 or m == 0xD8 or p + 2 > size:
+            return -1, h, w
+        L = (buf[p] << 8) | buf[p + 1]
+        if L < 2 or p + L > size:
+            return -1, h, w
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC) and h == 0 and L >= 7:
+            h, w = (buf[p + 3] << 8) | buf[p + 4], (buf[p + 5] << 8) | buf[p + 6]
+        p += L
+        if m == 0xDA:  # the entropy-coded bytes: up to the next marker
+            while True:
+                p = buf.find(b'\xff', p, size)
+                if p < 0 or p + 1 >= size:
+                    return -1, h, w
+                n = buf[p + 1]
+                if n == 0x00 or 0xD0 <= n <= 0xD7:
+                    p += 2
+                elif n == 0xFF:
+                    p += 1
+                else:
+                    break
+
+
+def write_mjpeg_avi(path, jpegs, fps='25:1', size=None):
+    """A minimal AVI file with one MJPG video stream: `jpegs` = the frames as whole JPEG files
+    (bytes), fps = 'num:den' (dwRate : dwScale), size = (height, width), by default read from the
+    first frame's header.  hdrl (avih, one strl with strh / strf), a movi list of 00dc chunks and
+    an idx1 index: what MJPEGReader, ffmpeg and OpenCV open."""
+    jpegs = [bytes(j) for j in jpegs]
+    if size is None:
+        _, h, w = _jpeg_walk(jpegs[0], 0, len(jpegs[0])) if jpegs else (0, 0, 0)
+    else:
+        h, w = size
+    num, den = (str(fps).split(':') + ['1'])[:2]
+    num, den = int(num), max(int(den), 1)
+    n, biggest = len(jpegs), max([len(j) for j in jpegs] + [0])
+
+    def chunk(cc, body):
+        return cc + struct.pack('<I', len(body)) + body + (b'\0' if len(body) & 1 else b'')
+
+    def lst(cc, body):
+        return b'LIST' + struct.pack('<I', len(body) + 4) + cc + body
+    avih = struct.pack('<14I', round(1e6 * den / max(num, 1)), 0, 0, 0x10, n, 0, 1, biggest, w, h, 0, 0, 0, 0)
+    strh = b'vids' + b'MJPG' + struct.pack('<IHHIIIIIIIIhhhh', 0, 0, 0, 0, den, num, 0, n, biggest, 0xFFFFFFFF, 0,
+                                           0, 0, w, h)
+    strf = struct.pack('<IiiHH', 40, w, h, 1, 24) + b'MJPG' + struct.pack('<IiiII', w * h * 3, 0, 0, 0, 0)
+    hdrl = lst(b'hdrl', chunk(b'avih', avih) + lst(b'strl', chunk(b'strh', strh) + chunk(b'strf', strf)))
+    movi, idx, at = [], [], 4  # idx1 offsets count from the 'movi' fourcc
+    for j in jpegs:
+        c = chunk(b'00dc', j)
+        idx.append(b'00dc' + struct.pack('<III', 0x10, at, len(j)))
+        movi.append(c)
+        at += len(c)
+    body = b'AVI ' + hdrl + lst(b'movi', b''.join(movi)) + chunk(b'idx1', b''.join(idx))
+    with open(path, 'wb') as f:
+        f.write(b'RIFF' + struct.pack('<I', len(body)) + body)
+
+
+class MJPEGReader:
+    """Motion-JPEG video: an AVI file whose first video stream is MJPG, or a raw stream of
+    concatenated JPEG files (.mjpeg / .mjpg, 25 fps as ffmpeg assumes).  .n_frames, .fps (rounded
+    as Y4MReader rounds), .fps_exact, .height, .width, frame_bytes(i), read(indices, device,
+    decoder) -> uint8 CUDA tensor [B,H,W,3] BGR.
+
+    The pixels are libjpeg's: what Pillow's Image.open(frame).convert('RGB') gives, in BGR, whether
+    a frame is decoded on the device or falls back to the host.  cv2.VideoCapture decodes MJPEG
+    through FFmpeg and converts colour with swscale, so its pixels can differ from these in low
+    bits; that difference has not been measured (no OpenCV here)."""
+
+    def __init__(self, path):
+        self.path = path
+        self._f = open(path, 'rb')
+        size = os.fstat(self._f.fileno()).st_size
+        if size == 0:
+            self._f.close()
+            raise ValueError('%s: empty file' % path)
+        self._mm = mmap.mmap(self._f.fileno(), 0, access=mmap.ACCESS_READ)
+        try:
+            if self._mm[:4] == b'RIFF':
+                spans, self.fps_exact = self._index_avi(size)
+            else:
+                spans, self.fps_exact = self._index_raw(size), 25.0
+            if not spans:
+                raise ValueError('%s: no video frames' % path)
+            if spans[0][1] == 0:
+                raise ValueError('%s: the first frame is empty' % path)
+            for i in range(1, len(spans)):  # an empty chunk repeats the frame before it
+                if spans[i][1] == 0:
+                    spans[i] = spans[i - 1]
+            end, self.height, self.width = _jpeg_walk(self._mm, spans[0][0], spans[0][0] + spans[0][1])
+            if self.height == 0 or self.width == 0:
+                raise ValueError('%s: the first frame is not a JPEG file' % path)
+        except Exception:
+            self.close()
+            raise
+        self.fps = round(self.fps_exact)
+        self.spans = spans
+        self.n_frames = len(spans)
+
+    def _index_avi(self, size):
+        mm, path = self._mm, self.path
+
+        def head(p, end):
+            """(fourcc, payload begin, payload size) of the chunk at p, or None past the end"""
+            if p + 8 > end:
+                return None
+            return mm[p:p + 4], p + 8, struct.unpack_from('<I', mm, p + 4)[0]
+        if size < 12 or mm[8:12] != b'AVI ':
+            raise ValueError('%s: a RIFF file that is not AVI, or a truncated header' % path)
+        vs, rate, spans = [None], [None], []  # the video stream's number, its frame rate
+
+        def walk_hdrl(p, end):
+            stream = -1
+            while True:
+                c = head(p, end)
+                if c is None:
+                    return
+                cc, b, n = c
+                if b + n > end:
+                    raise ValueError('%s: truncated AVI header' % path)
+                if cc == b'LIST' and n >= 4 and mm[b:b + 4] == b'strl':
+                    stream += 1
+                    q, strh, strf = b + 4, None, None
+                    while True:
+                        s = head(q, b + n)
+                        if s is None:
+                            break
+                        if s[1] + s[2] > b + n:
+                            raise ValueError('%s: truncated AVI header' % path)
+                        if s[0] == b'strh':
+                            strh = mm[s[1]:s[1] + s[2]]
+                        elif s[0] == b'strf':
+                            strf = mm[s[1]:s[1] + s[2]]
+                        q = s[1] + s[2] + (s[2] & 1)
+                    if vs[0] is None and strh is not None and len(strh) >= 28 and strh[:4] == b'vids':
+                        if strf is None or len(strf) < 20:
+                            raise ValueError('%s: truncated AVI header' % path)
+                        handler, comp = strh[4:8], strf[16:20]
+                        if b'MJPG' not in (handler.upper(), comp.upper()):
+                            four = comp if comp.strip(b'\0') else handler
+                            raise ValueError('%s: the video stream is %s, not Motion-JPEG (MJPG)'
+                                             % (path, four.decode('latin-1')))
+                        scale, r = struct.unpack_from('<II', strh, 20)
+                        vs[0], rate[0] = stream, r / max(scale, 1)
+                p = b + n + (n & 1)
+
+        def walk_movi(p, end):
+            want = (b'%02ddc' % vs[0], b'%02ddb' % vs[0]) if vs[0] < 100 else ()
+            while True:
+                c = head(p, end)
+                if c is None:
+                    return
+                cc, b, n = c
+                if cc == b'LIST' and n >= 4 and b + 4 <= end and mm[b:b + 4] == b'rec ':
+                    walk_movi(b + 4, min(b + n, end))
+                elif cc in want:
+                    if b + n > end:
+                        return  # a truncated last frame is not a frame
+                    spans.append((b, n))
+                p = b + n + (n & 1)
+
+        p = 0
+        while True:  # RIFF 'AVI ', then any number of RIFF 'AVIX'
+            c = head(p, size)
+            if c is None or c[0] != b'RIFF' or c[1] + 4 > size:
+                break
+            cc, b, n = c
+            end, q = min(b + n, size), b + 4
+            form = mm[b:b + 4]
+            while form in (b'AVI ', b'AVIX'):
+                s = head(q, end)
+                if s is None:
+                    break
+                if s[0] == b'LIST' and s[2] >= 4 and s[1] + 4 <= end:
+                    kind = mm[s[1]:s[1] + 4]
+                    if kind == b'hdrl' and form == b'AVI ':
+                        if s[1] + s[2] > end:
+                            raise ValueError('%s: truncated AVI header' % path)
+                        walk_hdrl(s[1] + 4, s[1] + s[2])
+                        if vs[0] is None:
+                            raise ValueError('%s: no video stream' % path)
+                    elif kind == b'movi':
+                        if vs[0] is None:
+                            raise ValueError('%s: no stream headers before the frames' % path)
+                        walk_movi(s[1] + 4, min(s[1] + s[2], end))
+                q = s[1] + s[2] + (s[2] & 1)
+            p = b + n + (n & 1)
+        if vs[0] is None:
+            raise ValueError('%s: truncated AVI header' % path)
+        return spans, rate[0]
+
+    def _index_raw(self, size):
+        spans, p = [], 0
+        while p < size:
+            end, _, _ = _jpeg_walk(self._mm, p, size)
+            if end < 0:
+                break  # trailing bytes that are no whole frame are dropped
+            spans.append((p, end - p))
+            p = end
+        if not spans:
+            raise ValueError('%s: not a stream of JPEG files' % self.path)
+        return spans
+
+    def close(self):
+        if self._mm is not None:
+            self._mm.close()
+            self._f.close()
+            self._mm = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def frame_bytes(self, i):
+        """the compressed bytes of frame i (an empty chunk gives the frame before it)"""
+        o, n = self.spans[i]
+        return self._mm[o:o + n]
+
+    def _host_frame(self, i, data):
+        import io
+        from PIL import Image
+        try:
+            img = np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))
+        except Exception as e:
+            raise ValueError('%s: frame %d does not decode: %s' % (self.path, i, e))
+        if img.shape[:2] != (self.height, self.width):
+            raise ValueError('%s: frame %d is %d x %d, the first frame %d x %d'
+                             % (self.path, i, img.shape[1], img.shape[0], self.width, self.height))
+        return img[:, :, ::-1]
+
+    def read(self, indices, device=None, decoder='device', seg_bytes=0):
+        """BGR frames [B,H,W,3] uint8 in HBM of `device` (default cuda:0).  decoder='device': the
+        frames' compressed bytes go to vtf_jpeg_decode_split in one call, which decodes them
+        straight into the result (its slots are the frames); a frame the device does not decode
+        (4:4:4 / 4:2:2 sampling, restart intervals, no DHT segment, progressive, a corrupt scan) is
+        decoded with Pillow on the host and copied into its slot: the same pixels either way.
+        decoder='host' decodes every frame with Pillow and uploads the pixels.  Indices may repeat
+        and come in any order.  A frame of another size than the first is a ValueError."""
+        import torch
+        from . import _native as nat
+        if decoder not in ('device', 'host'):
+            raise ValueError("decoder must be 'device' or 'host'")
+        dev = nat.require_gpu(device)
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n_frames):
+            raise IndexError('frame index out of range [0, %d)' % self.n_frames)
+        H, W = self.height, self.width
+        # every distinct frame is decoded once (an index may repeat; so may an empty chunk's frame)
+        at = [self.spans[i][0] for i in idx.tolist()]
+        uniq, inv = np.unique(np.asarray(at, np.int64), return_inverse=True)
+        frame_at = dict(zip(at, idx.tolist()))
+        order = [frame_at[int(o)] for o in uniq]  # a frame index for every distinct frame
+        n = len(order)
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+        if n == 0:
+            return out
+        files = [self.frame_bytes(i) for i in order]
+        if decoder == 'host':
+            host = np.stack([self._host_frame(i, f) for i, f in zip(order, files)])
+            out.copy_(torch.from_numpy(host))
+        else:
+            sizes, status = np.zeros((n, 2), np.int32), np.zeros(n, np.int32)
+            offs = np.zeros(n + 1, np.int64)
+            np.cumsum([len(f) for f in files], out=offs[1:])
+            data = np.frombuffer(b''.join(files), np.uint8)
+            with torch.cuda.device(dev):
+                nat.check(nat.lib().vtf_jpeg_decode_split(data.ctypes.data, offs.ctypes.data, n, nat.ptr(out), H, W,
+                                                          out.stride(0), out.stride(1), sizes.ctypes.data,
+                                                          status.ctypes.data, int(seg_bytes), nat.stream_ptr(dev)))
+            for k in range(n):
+                if status[k] == 0 and (int(sizes[k, 0]), int(sizes[k, 1])) != (H, W):
+                    raise ValueError('%s: frame %d is %d x %d, the first frame %d x %d'
+                                     % (self.path, order[k], sizes[k, 1], sizes[k, 0], W, H))
+                if status[k] != 0:
+                    out[k].copy_(torch.from_numpy(np.ascontiguousarray(self._host_frame(order[k], files[k]))))
+        if n == idx.size and np.array_equal(inv, np.arange(n)):
+            return out
+        return out.index_select(0, torch.from_numpy(np.asarray(inv, np.int64)).to(dev))
