@@ -1,5 +1,6 @@
-"""Inputs shared by tests/test_mjpeg.py (the split decoder against the serial one on the CPU) and
-tests/test_jpeg_split_gpu.py (the same files through the kernel)."""
+"""Shared by the JPEG tests: Pillow as the encoder and decoder to compare with, a file with a restart
+interval, and the inputs of tests/test_mjpeg.py (the split decoder against the serial one on the
+CPU) and tests/test_jpeg_split_gpu.py (the same files through the kernel)."""
 import io
 
 import numpy as np
@@ -12,6 +13,17 @@ def pillow_jpeg(img, **kw):
     buf = io.BytesIO()
     (img if isinstance(img, Image.Image) else Image.fromarray(np.ascontiguousarray(img))).save(buf, 'JPEG', **kw)
     return buf.getvalue()
+
+
+def pillow_bgr(data):
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))[:, :, ::-1]
+
+
+def with_dri(data, interval=4):
+    """the file with a DRI segment inserted before its SOS"""
+    at = data.index(b'\xff\xda')
+    return data[:at] + b'\xff\xdd\x00\x04' + interval.to_bytes(2, 'big') + data[at:]
 
 
 def content(kind, h, w, rng):

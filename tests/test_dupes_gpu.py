@@ -65,3 +65,34 @@ def test_ahash_vs_oracle():
     for c, h in zip(crops, got):
         f, x1, y1, x2, y2 = c
         np.testing.assert_array_equal(unpack_hash(h), od.ahash(fr[f, y1:y2, x1:x2]), err_msg=str(c))
+
+
+def test_ahash_crops_on_frames_with_unpacked_pixels():
+    """A view whose pixels are 6 bytes apart is hashed as its packed copy is."""
+    from videotofaces.dupes import ahash_crops
+    base = torch.from_numpy(np.random.default_rng(8).integers(0, 256, (2, 16, 32, 3), dtype=np.uint8)).cuda()
+    view = base[:, :, ::2]
+    assert view.shape == (2, 16, 16, 3) and view.stride(2) == 6
+    crops = [[0, 0, 0, 16, 16], [1, 2, 3, 14, 15]]
+    assert ahash_crops(view, crops).tolist() == ahash_crops(view.contiguous(), crops).tolist()
+
+
+def test_frames_args_rejects_device_tensors_of_the_wrong_kind():
+    """Every term of the check on CUDA tensors (tests/test_resize.py can only offer it CPU ones), the
+    device mismatch, and the copy of unpacked pixels; nothing here reaches the library."""
+    from videotofaces._native import frames_args
+    ok = torch.zeros((2, 8, 8, 3), dtype=torch.uint8, device='cuda:0')
+    four = torch.zeros((2, 8, 8, 4), dtype=torch.uint8, device='cuda:0')
+    for bad in (ok.float(), ok.to(torch.int8), ok[0], ok[..., :2], four):  # dtype, rank, channels
+        with pytest.raises(ValueError, match=r'frames must be a CUDA uint8 tensor \[B,H,W,3\]'):
+            frames_args(bad)
+    with pytest.raises(ValueError, match='is on cuda:0, not on cuda:1'):
+        frames_args(ok, 'cuda:1')
+    t, args = frames_args(ok, 'cuda:0')
+    assert t is ok and args[0].value == ok.data_ptr() and tuple(args[1:]) == (2, 8, 8, 192, 24)
+    view = torch.zeros((2, 8, 16, 3), dtype=torch.uint8, device='cuda:0')[:, :, ::2]
+    t, args = frames_args(view)
+    assert t.is_contiguous() and t.data_ptr() != view.data_ptr() and tuple(args[1:]) == (2, 8, 8, 192, 24)
+    rows = torch.zeros((2, 16, 8, 3), dtype=torch.uint8, device='cuda:0')[:, ::2]  # packed pixels, strided rows: no copy
+    t, args = frames_args(rows)
+    assert t is rows and tuple(args[1:]) == (2, 8, 8, 384, 48)

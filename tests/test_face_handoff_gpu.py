@@ -7,7 +7,6 @@ HBM and gives the host path's embeddings bit for bit without opening their files
 first differing block in a failure message.  No test here feeds a kernel a damaged scan.
 """
 import ctypes
-import io
 import os
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 import torch
 
 import jpeg_decode_twin as twin
+from jpeg_split_inputs import pillow_bgr
 
 pytestmark = pytest.mark.gpu
 
@@ -24,11 +24,6 @@ E_ARG, E_CAPACITY = -1, -3
 SIZES = [(1, 1), (1, 2), (2, 1), (9, 3), (9, 4), (9, 5), (7, 9), (8, 8), (15, 17), (16, 16), (17, 15), (33, 31),
          (50, 50), (113, 131), (63, 257)]
 FH, FW = 180, 320
-
-
-def pillow_bgr(data):
-    from PIL import Image
-    return np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))[:, :, ::-1]
 
 
 _FRAMES = {}
@@ -298,14 +293,21 @@ def test_mixed_store(tmp_path, monkeypatch, decoder):
     by_file = [paths[i] for i in (1, 3, 4, 5, 6, 7)]
     host = grouping.encode_faces(paths, model, 3, None)
     read = []
-    real_imread, real_decode = grouping._imread, utils.jpeg_decode
+    gathered = []  # the stored faces of every faces_to_atlas call
+    real_imread, real_decode, real_atlas = grouping._imread, utils.jpeg_decode, utils.faces_to_atlas
     monkeypatch.setattr(grouping, '_imread', lambda p: read.append(p) or real_imread(p))
     monkeypatch.setattr(utils, 'jpeg_decode', lambda files, *a, **k: read.extend(['?'] * len(files)) or
                         real_decode(files, *a, **k))
+    monkeypatch.setattr(utils, 'faces_to_atlas', lambda faces, *a, **k:
+                        gathered.append(sum(f is not None for f in faces)) or real_atlas(faces, *a, **k))
     monkeypatch.setattr(grouping, 'DECODE_GROUP', 3)  # a group of stored and unstored, one of files only
     got = grouping.encode_faces(paths, model, 3, None, jpeg_decoder=decoder, store=store)
     assert np.array_equal(got, host)
     assert read == by_file if decoder == 'host' else read == ['?'] * len(by_file)
+    # one call for the one group that has stored faces (paths 0 and 2), with both of them
+    assert [g for g in gathered if g] == [2]
+    if decoder == 'device':
+        assert gathered == [2]  # a group of files only is decoded straight into its atlas
 
 
 def test_video_to_faces_handoff_equals_files(tmp_path, monkeypatch):

@@ -1,11 +1,11 @@
 """CPU: the JPEG twin (tests/jpeg_twin.py) writes Pillow's bytes, the library exports the device
 encoder's entry point, and the jpeg_encoder keyword is validated before any device work."""
 import ctypes
-import io
 
 import numpy as np
 import pytest
 
+import jpeg_split_inputs
 import jpeg_twin
 
 SIZES = [(1, 1), (8, 8), (15, 16), (16, 15), (24, 9), (50, 50), (31, 47), (96, 80)]  # (w, h)
@@ -22,10 +22,7 @@ def content(kind, h, w, rng):
 
 
 def pillow_jpeg(rgb, quality):
-    from PIL import Image
-    buf = io.BytesIO()
-    Image.fromarray(np.ascontiguousarray(rgb)).save(buf, 'JPEG', quality=quality)
-    return buf.getvalue()
+    return jpeg_split_inputs.pillow_jpeg(rgb, quality=quality)
 
 
 @pytest.mark.parametrize('quality', [1, 30, 75, 95, 100])

@@ -14,6 +14,7 @@ import pytest
 import jpeg_decode_twin as twin
 import jpeg_twin
 from conftest import ROOT
+from jpeg_split_inputs import pillow_jpeg, with_dri
 
 SIZES = [(1, 1), (1, 2), (2, 1), (7, 9), (8, 8), (16, 16), (17, 15), (31, 33), (50, 50), (113, 131)]  # (h, w)
 
@@ -26,13 +27,6 @@ def content(kind, h, w, rng):
         return (rng.integers(0, 2, (h, w, 3)) * 255).astype(np.uint8)
     yy, xx = np.mgrid[0:h, 0:w]
     return np.stack([(xx * 3 + yy) % 256, (yy * 2 + 40) % 256, (xx + yy * 2) % 256], -1).astype(np.uint8)
-
-
-def pillow_jpeg(img, **kw):
-    from PIL import Image
-    buf = io.BytesIO()
-    (img if isinstance(img, Image.Image) else Image.fromarray(np.ascontiguousarray(img))).save(buf, 'JPEG', **kw)
-    return buf.getvalue()
 
 
 def pillow_rgb(data):
@@ -73,12 +67,6 @@ def probe(data):
     assert L.vtf_jpeg_probe(bytes(data), len(data), info.ctypes.data) == 0
     return dict(h=int(info[0]), w=int(info[1]), kind=int(info[2]), scan_begin=int(info[3]), scan_end=int(info[4]),
                 why=int(info[5]), ncomp=int(info[6]))
-
-
-def with_dri(data, interval=4):
-    """the file with a DRI segment inserted before its SOS"""
-    at = data.index(b'\xff\xda')
-    return data[:at] + b'\xff\xdd\x00\x04' + interval.to_bytes(2, 'big') + data[at:]
 
 
 def segments(data):
@@ -219,3 +207,26 @@ def test_encode_faces_rejects_unknown_decoder():
     from videotofaces.grouping import encode_faces
     with pytest.raises(ValueError):
         encode_faces(['x.jpg'], None, 4, None, jpeg_decoder='nope')
+
+
+def test_jpeg_decode_out_validated_without_a_gpu():
+    """A bad `out` is a ValueError before any device work (a CPU tensor is one as well, so every case
+    here ends before the GPU is asked for)."""
+    import torch
+    from videotofaces.utils import jpeg_decode
+    files = [pillow_jpeg(np.zeros((8, 8, 3), np.uint8), quality=90)] * 2
+    for bad in (torch.zeros((2, 8, 8, 3), dtype=torch.float32),   # dtype
+                torch.zeros((3, 8, 8, 3), dtype=torch.uint8),     # three slots for two files
+                torch.zeros((2, 8, 8), dtype=torch.uint8), np.zeros((2, 8, 8, 3), np.uint8)):
+        with pytest.raises(ValueError, match='out must be a CUDA uint8 tensor'):
+            jpeg_decode(files, out=bad)
+
+
+def test_file_table():
+    from videotofaces._native import file_table
+    data, offs = file_table([])
+    assert data.dtype == np.uint8 and data.tolist() == [0] and offs.dtype == np.int64 and offs.tolist() == [0]
+    data, offs = file_table([b'', b'ab'])
+    assert data.tobytes() == b'ab' and offs.dtype == np.int64 and offs.tolist() == [0, 0, 2]
+    data, offs = file_table([b'', b''])
+    assert data.tolist() == [0] and offs.tolist() == [0, 0, 0]

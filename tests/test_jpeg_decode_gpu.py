@@ -6,7 +6,6 @@ tests/test_jpeg_decode.py) is used only to say, in a failure message, which file
 differs first.  No test here feeds a kernel a damaged scan: corrupt streams are exercised on the
 CPU only (tests/host/jpeg_decode_fuzz.cpp).
 """
-import io
 import os
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 import torch
 
 import jpeg_decode_twin as twin
+from jpeg_split_inputs import pillow_bgr, pillow_jpeg
 
 pytestmark = pytest.mark.gpu
 
@@ -22,18 +22,6 @@ CASES = [(h, w, 95) for h, w in [(1, 1), (1, 2), (2, 1), (7, 9), (8, 8), (15, 17
                                  (50, 50), (113, 131), (160, 160), (63, 257)]]
 CASES += [(h, w, q) for h, w in [(17, 15), (50, 50)] for q in (1, 50, 100)]
 E_ARG = -1
-
-
-def pillow_jpeg(rgb, **kw):
-    from PIL import Image
-    buf = io.BytesIO()
-    (rgb if isinstance(rgb, Image.Image) else Image.fromarray(np.ascontiguousarray(rgb))).save(buf, 'JPEG', **kw)
-    return buf.getvalue()
-
-
-def pillow_bgr(data):
-    from PIL import Image
-    return np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))[:, :, ::-1]
 
 
 def content(kind, h, w, rng):
@@ -138,9 +126,7 @@ def raw_call(files, buf, Hmax, Wmax, frame_stride, row_stride, data=True, offset
     """vtf_jpeg_decode on a flat CUDA uint8 buffer -> (rc, sizes, status)"""
     from videotofaces import _native as nat
     n = len(files) if n is None else n
-    blob = np.frombuffer(b''.join(files) or b'\0', np.uint8)
-    offs = np.zeros(len(files) + 1, np.int64)
-    np.cumsum([len(f) for f in files], out=offs[1:])
+    blob, offs = nat.file_table(files)
     if offsets is not None:
         offs = np.asarray(offsets, np.int64)
     sizes, status = np.full((max(n, 1), 2), -9, np.int32), np.full(max(n, 1), -9, np.int32)
@@ -232,7 +218,7 @@ def test_encode_faces_groups_caps_and_oversize_files(tmp_path, monkeypatch):
     cap that ends groups early, files above the side limit (groups of their own) in the middle and
     as the last file, host-decoded files (progressive, grayscale) first in a group, inside one, and
     as the file that trips the cap, and a batch size that divides no group."""
-    from videotofaces import grouping
+    from videotofaces import grouping, utils
     from videotofaces.encoders.facenet import FaceNet
     rng = np.random.default_rng(33)
     # (h, w, keyword arguments of the writer); 'L' = grayscale
@@ -254,16 +240,26 @@ def test_encode_faces_groups_caps_and_oversize_files(tmp_path, monkeypatch):
     monkeypatch.setattr(grouping, 'DECODE_MAX_SIDE', 120)
     monkeypatch.setattr(grouping, 'DECODE_ATLAS_BYTES', 3 * 100 * 90 * 3)
     # the groups this must make
-    at, groups = 0, []
+    at, groups, decodable = 0, [], 0
     while at < len(paths):
-        files, probed, on_host, hm, wm = grouping._decode_group(paths, at)
+        files, probed, on_host, stored, hm, wm = grouping._next_group(paths, at, None, 'device')
+        assert not stored
+        decodable += len(on_host) < len(files)
         assert 1 <= len(files) <= 4 and sorted(on_host) == [i for i in range(len(files)) if probed[i][2] != 0
                                                              or max(probed[i][:2]) > 120]
         assert len(files) == 1 or (len(files) * hm * wm * 3 <= 3 * 100 * 90 * 3 and max(hm, wm) <= 120)
         groups.append(len(files))
         at += len(files)
     assert groups == [4, 3, 1, 1, 2, 1, 4, 1, 1], groups
+    # one decode call per group that has a file for the device, straight into the group's atlas
+    calls = {'decode': 0, 'atlas': 0}
+    real_decode, real_atlas = utils.jpeg_decode, utils.faces_to_atlas
+    monkeypatch.setattr(utils, 'jpeg_decode', lambda *a, **k: calls.update(decode=calls['decode'] + 1) or
+                        real_decode(*a, **k))
+    monkeypatch.setattr(utils, 'faces_to_atlas', lambda *a, **k: calls.update(atlas=calls['atlas'] + 1) or
+                        real_atlas(*a, **k))
     dev = grouping.encode_faces(paths, model, 5, area, jpeg_decoder='device')
+    assert calls == {'decode': decodable, 'atlas': 0} and decodable == 5
     assert host.shape == (len(spec), 512)
     assert np.array_equal(host, dev)
 
@@ -341,3 +337,25 @@ def test_video_to_faces_device_decoder_equals_host(tmp_path):
     for a, b in zip(rows['host'][1:], rows['device'][1:]):
         assert a[:2] == b[:2]  # the cluster count and the silhouette score (no atomic sums behind it): the same text
         np.testing.assert_allclose([float(v) for v in a[1:]], [float(v) for v in b[1:]], rtol=rtol, atol=0)
+
+
+def test_jpeg_decode_out_checked_on_device_tensors():
+    """Every term of the check of `out` on CUDA tensors (tests/test_jpeg_decode.py can only offer it
+    CPU ones): each is a ValueError before the library is called, and `out` keeps its bytes."""
+    from videotofaces.utils import jpeg_decode
+    rng = np.random.default_rng(35)
+    files = [pillow_jpeg(content('noise', 16, 24, rng), quality=90) for _ in range(2)]
+    ok = torch.full((2, 16, 24, 3), 0xA5, dtype=torch.uint8, device='cuda:0')
+    wide = torch.full((2, 16, 48, 3), 0xA5, dtype=torch.uint8, device='cuda:0')
+    for bad in (ok.float(), ok[:1], torch.cat([ok, ok]), ok[0], ok[..., :2], wide[:, :, ::2]):  # dtype, N, rank, pixels
+        with pytest.raises(ValueError, match='out must be a CUDA uint8 tensor'):
+            jpeg_decode(files, out=bad)
+    with pytest.raises(ValueError, match='out is smaller than a file'):
+        jpeg_decode(files, probed=[(16, 24, 0), (17, 24, 0)], out=ok)
+    with pytest.raises(ValueError, match='out is on cuda:0, not on cuda:1'):
+        jpeg_decode(files, 'cuda:1', out=ok)
+    assert (ok == 0xA5).all() and (wide == 0xA5).all()
+    # a file the probe calls undecodable may be larger than a slot: the caller fills it
+    atlas, sizes, status = jpeg_decode(files, 'cuda', probed=[(16, 24, 0), (99, 99, 1)], out=ok)
+    assert atlas is ok and status.tolist() == [0, 0] and sizes.tolist() == [[16, 24]] * 2
+    assert np.array_equal(ok.cpu().numpy(), np.stack([pillow_bgr(f) for f in files]))

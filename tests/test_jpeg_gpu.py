@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import jpeg_split_inputs
 import jpeg_twin
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,7 @@ SIZES = [(1, 1), (8, 8), (15, 16), (16, 15), (24, 9), (50, 50), (31, 47), (96, 8
 
 
 def pillow_jpeg(bgr, quality):
-    from PIL import Image
-    buf = io.BytesIO()
-    Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1])).save(buf, 'JPEG', quality=quality)
-    return buf.getvalue()
+    return jpeg_split_inputs.pillow_jpeg(bgr[:, :, ::-1], quality=quality)
 
 
 _FRAMES = {}

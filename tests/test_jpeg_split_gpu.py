@@ -5,23 +5,17 @@ Motion-JPEG AVI file to the same face files as the decoded frames give.
 Pillow (libjpeg-turbo) is the checker, as in tests/test_jpeg_decode_gpu.py.  No test here feeds a
 kernel a damaged scan: those are exercised on the CPU only (tests/host/jpeg_split_check.cpp).
 """
-import io
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from jpeg_split_inputs import content, pillow_jpeg, split_inputs
+from jpeg_split_inputs import content, pillow_bgr, pillow_jpeg, split_inputs
 
 pytestmark = pytest.mark.gpu
 
 E_ARG = -1
-
-
-def pillow_bgr(data):
-    from PIL import Image
-    return np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))[:, :, ::-1]
 
 
 _BATCH = {}
@@ -64,9 +58,7 @@ def raw_call(files, buf, Hmax, Wmax, frame_stride, row_stride, seg_bytes=0, n=No
     """vtf_jpeg_decode_split on a flat CUDA uint8 buffer -> (rc, sizes, status)"""
     from videotofaces import _native as nat
     n = len(files) if n is None else n
-    blob = np.frombuffer(b''.join(files) or b'\0', np.uint8)
-    offs = np.zeros(len(files) + 1, np.int64)
-    np.cumsum([len(f) for f in files], out=offs[1:])
+    blob, offs = nat.file_table(files)
     sizes, status = np.full((max(n, 1), 2), -9, np.int32), np.full(max(n, 1), -9, np.int32)
     rc = nat.lib().vtf_jpeg_decode_split(blob.ctypes.data, offs.ctypes.data, n, nat.ptr(buf), Hmax, Wmax, frame_stride,
                                          row_stride, sizes.ctypes.data, status.ctypes.data, seg_bytes,
@@ -124,7 +116,8 @@ def clip_frames(n=6, h=96, w=128, seed=5, odd=None):
     return [pillow_jpeg(f[:, :, ::-1], quality=90, **(dict(subsampling=0) if i == odd else {})) for i, f in enumerate(fr)]
 
 
-def test_mjpeg_reader_read(tmp_path):
+def test_mjpeg_reader_read(tmp_path, monkeypatch):
+    from videotofaces import utils
     from videotofaces.video import MJPEGReader, write_mjpeg_avi
     jpegs = clip_frames()
     want = np.stack([pillow_bgr(j) for j in jpegs])
@@ -142,6 +135,16 @@ def test_mjpeg_reader_read(tmp_path):
     with pytest.raises(IndexError):
         r.read([6])
     assert np.array_equal(MJPEGReader(raw).read(idx).cpu().numpy(), want[idx])
+    # read() decodes into the tensor it returns: jpeg_decode gets it as `out` and gives it back
+    outs, real_decode = [], utils.jpeg_decode
+
+    def decode(files, *a, out=None, **k):
+        res = real_decode(files, *a, out=out, **k)
+        outs.append((out.data_ptr(), tuple(out.shape), res[0].data_ptr()))
+        return res
+    monkeypatch.setattr(utils, 'jpeg_decode', decode)
+    got = r.read(list(range(6)))
+    assert outs == [(got.data_ptr(), (6, 96, 128, 3), got.data_ptr())] and np.array_equal(got.cpu().numpy(), want)
 
 
 def test_mjpeg_reader_host_fallback_and_sizes(tmp_path):

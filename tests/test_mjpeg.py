@@ -12,13 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from jpeg_split_inputs import content, pillow_jpeg, split_inputs
-
-
-def with_dri(data, interval=4):
-    """the file with a DRI segment inserted before its SOS (tests/test_jpeg_decode.py's helper)"""
-    at = data.index(b'\xff\xda')
-    return data[:at] + b'\xff\xdd\x00\x04' + interval.to_bytes(2, 'big') + data[at:]
+from jpeg_split_inputs import content, pillow_jpeg, split_inputs, with_dri
 
 
 def frames(n, h=32, w=48, seed=0, **kw):

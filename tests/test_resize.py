@@ -88,6 +88,33 @@ def test_resize_crops_arguments_validated_without_a_gpu():
         resize_crops(cpu, [[0, 5, 5, 5, 9]], 100)
 
 
+def test_frames_args_and_crop_table_without_a_gpu():
+    from videotofaces._native import crop_table, frames_args
+    cpu = torch.zeros((1, 8, 8, 3), dtype=torch.uint8)
+    for bad in (cpu, cpu.numpy(), cpu.float(), cpu[0], cpu[..., :2]):  # a CPU tensor, no tensor, dtype, rank, pixels
+        with pytest.raises(ValueError, match=r'frames must be a CUDA uint8 tensor \[B,H,W,3\]'):
+            frames_args(bad)
+    c = crop_table([[0, 1, 2, 3, 4], (1, 5, 6, 7, 8)])
+    assert c.dtype == np.int32 and c.shape == (2, 5) and c.flags['C_CONTIGUOUS'] and c[1].tolist() == [1, 5, 6, 7, 8]
+    assert crop_table(np.arange(20, dtype=np.int64).reshape(2, 10)[:, ::2]).tolist() == [[0, 2, 4, 6, 8], [10, 12, 14, 16, 18]]
+    assert crop_table([]).shape == (0, 5)
+
+
+def test_slot_rects_and_pack_atlas():
+    from videotofaces.utils import pack_atlas, slot_rects
+    rng = np.random.default_rng(5)
+    images = [rng.integers(1, 256, (h, w, 3), dtype=np.uint8) for h, w in [(5, 9), (12, 4), (7, 7)]]
+    atlas, sizes = pack_atlas(images)
+    assert atlas.dtype == np.uint8 and atlas.shape == (3, 12, 9, 3) and atlas.flags['C_CONTIGUOUS']
+    assert sizes.dtype == np.int32 and sizes.tolist() == [[5, 9], [12, 4], [7, 7]]
+    for i, im in enumerate(images):
+        h, w = im.shape[:2]
+        assert np.array_equal(atlas[i, :h, :w], im) and not atlas[i, h:].any() and not atlas[i, :, w:].any()
+    rects = slot_rects(sizes)
+    assert rects.dtype == np.int32 and rects.tolist() == [[0, 0, 0, 9, 5], [1, 0, 0, 4, 12], [2, 0, 0, 7, 7]]
+    assert slot_rects(np.zeros((0, 2), np.int32)).shape == (0, 5)
+
+
 def test_process_frames_batch_still_validates_its_keywords():
     from videotofaces.detection import RESIZE_ATLAS_BYTES, process_frames_batch
     assert RESIZE_ATLAS_BYTES == 1 << 30

@@ -29,7 +29,7 @@
 // the end.
 //
 // vtf_jpeg_encode_crops_decoded is the same call (encode_crops below) with two more launches
-// before the last sync: k_jpeg_idct and k_jpeg_pixels of jpeg_recon.hpp, the decoder's own
+// before the last sync: k_jpeg_idct and k_jpeg_pixels of jpeg_recon.hip, the decoder's own
 // reconstruction stage, turn k_jpeg_mcu's coefficient buffer (exactly what a decoder's Huffman
 // stage would rebuild from the file) into the pixels libjpeg decodes from each file, tightly
 // packed in HBM for the grouping stage.

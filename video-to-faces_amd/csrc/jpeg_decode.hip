@@ -14,7 +14,7 @@
 //                   share one table set (the host de-duplicates the sets; nearly every file uses
 //                   Annex K's); otherwise lane 0 reads its file's set from global memory.
 //                   Coefficients: int16 [mcu][6][64], zigzag order, zeroed beforehand.
-//   k_jpeg_idct,    stage 2 (jpeg_recon.hpp, shared with the encoder): dequantisation, IDCT,
+//   k_jpeg_idct,    stage 2 (jpeg_recon.hip, shared with the encoder): dequantisation, IDCT,
 //   k_jpeg_pixels   upsampling and colour conversion into the file's slot.  Only rows < h and
 //                   columns < w are written.  A file whose column pass leaves the int16 range (no
 //                   8-bit image does) is marked corrupt: host fallback.
@@ -75,8 +75,6 @@ __global__ __launch_bounds__(64 * FILES_PER_WG) void k_jpeg_entropy(const uint8_
         st = jpg::entropy_decode(data, d.scan_begin, d.scan_end, sets + d.set, mcus, out);
     status[f] = st;
 }
-
-static_assert(jpg::ST_OK == RECON_OK && jpg::ST_CORRUPT == RECON_WILD, "jpeg_recon.hpp's statuses are the decoder's");
 
 // ---------------------------------------------------------------------------------- gather
 // one face of vtf_faces_to_atlas: tight [h][w][3] pixels at src (null: the slot is left alone)

@@ -8,6 +8,7 @@ library binds to (same soname, libamdhip64.so.7).
 import ctypes
 import os
 
+import numpy as np
 import torch  # noqa: F401  (loads the HIP runtime first)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -227,3 +228,28 @@ def frames_view(imgs, device=None):
         x = np.ascontiguousarray(x)
     B, H, W = x.shape[:3]
     return _c.c_void_p(x.ctypes.data), 0, B, H, W, x.strides[0], x.strides[1], x
+
+
+def frames_args(t, device=None):
+    """frames_view for the kernels that read crops of frames in HBM: a CUDA uint8 tensor [B,H,W,3] (on `device`
+    when given), copied where its pixels are not packed -> (it, (base pointer, B, H, W, frame_stride, row_stride))."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[3] == 3):
+        raise ValueError('frames must be a CUDA uint8 tensor [B,H,W,3]')
+    if device is not None and t.device != torch.device(device):
+        raise ValueError('frames tensor is on %s, not on %s' % (t.device, device))
+    if t.stride(3) != 1 or t.stride(2) != 3:
+        t = t.contiguous()
+    return t, (ptr(t), *t.shape[:3], t.stride(0), t.stride(1))
+
+
+def crop_table(crops):
+    """Crop rectangles (frame, x1, y1, x2, y2) as the library takes them: contiguous int32 [N,5]."""
+    return np.ascontiguousarray(np.asarray(crops, np.int32).reshape(-1, 5))
+
+
+def file_table(files):
+    """A list of N `bytes` as the library takes files: (uint8 array of the joined bytes, int64
+    offsets [N+1]).  An empty join is one zero byte, so that the array has an address."""
+    offs = np.zeros(len(files) + 1, np.int64)
+    np.cumsum([len(f) for f in files], dtype=np.int64, out=offs[1:])
+    return np.frombuffer(b''.join(files) or b'\0', np.uint8), offs

@@ -9,6 +9,7 @@ device (vtf_boxes_to_crops, csrc/boxes.hip) straight on the detector's rows in H
 (vtf_*_encode_crops), replacing the reference's JPEG write/read hand-off.
 """
 import ctypes
+import os.path as osp
 
 import numpy as np
 
@@ -130,7 +131,6 @@ def frame_source(path, video_reader='opencv', device=None, mjpeg_reader='auto'):
     in-memory uint8 array (fps 1).  mjpeg_reader: 'device' / 'host' read .avi, .mjpeg and .mjpg
     files as Motion-JPEG with video.MJPEGReader and that decoder (frames in HBM, libjpeg's pixels);
     'auto' does so, on the device, only where OpenCV is not installed."""
-    import numpy as np
     if mjpeg_reader not in ('auto', 'device', 'host'):
         raise ValueError("mjpeg_reader must be 'auto', 'device' or 'host'")
     if isinstance(path, np.ndarray):
@@ -213,10 +213,8 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     store (a facestore.FaceStore, with the device encoder): the encoder also leaves every saved
     face's decoded pixels in HBM, and the store keeps them under the file's path for encode_faces.
     The files are written all the same.  The host path stores nothing."""
-    import os.path as osp
-    import numpy as np
     import torch
-    from .dupes import ahash_crops, ahash, nearest_dupes
+    from .dupes import ahash_crops, ahash
     from .utils import resize_keep_ratio, imwrite
     from . import _native as nat
     if jpeg_encoder not in ('host', 'device'):
@@ -240,23 +238,42 @@ def process_frames_batch(frames, indices, model, det_params, save_params, hash_t
     if jpeg_encoder == 'device' and (not resize_to or _resize_on_device(rects, resize_to)):
         return _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, hashes, store,
                                   resize_to), hashes
-    faces, seen = [], {}
-    for fi, x1, y1, x2, y2 in rects.tolist():
-        j = seen.get(fi, 0)
-        seen[fi] = j + 1
-        faces.append((frames[fi][y1:y2, x1:x2], out_prefix + '%06d_%u.jpg' % (indices[fi], j)))
+    names = _face_names(rects, indices, out_prefix)
+    faces = [frames[fi][y1:y2, x1:x2] for fi, x1, y1, x2, y2 in rects.tolist()]
     if resize_to:
-        faces = [(resize_keep_ratio(img, resize_to), fn) for (img, fn) in faces]
+        faces = [resize_keep_ratio(img, resize_to) for img in faces]
     if hash_thr and hash_thr != -1 and faces:
         if resize_to:  # the reference hashes the resized face (detection.py:149-153)
-            hs = [int(sum(int(v) << k for k, v in enumerate(ahash(img, fr_dev.device)))) for img, _ in faces]
+            hs = [int(sum(int(v) << k for k, v in enumerate(ahash(img, fr_dev.device)))) for img in faces]
         else:
             hs = ahash_crops(fr_dev, rects)
-        flags, _ = nearest_dupes(list(zip(hs, [fn for _, fn in faces])), hashes, hash_thr)
-        faces = [f for f, d in zip(faces, flags) if not d]
-    for img, fn in faces:
-        imwrite(osp.join(out_dir, 'faces', fn), np.ascontiguousarray(img))
-    return [fn for _, fn in faces], hashes
+        keep = _dedupe_nearest(hs, names, hashes, hash_thr)
+        faces, names = [faces[i] for i in keep], [names[i] for i in keep]
+    for img, fn in zip(faces, names):
+        imwrite(_face_path(out_dir, fn), np.ascontiguousarray(img))
+    return names, hashes
+
+
+def _face_names(rects, indices, prefix):
+    """The file names of a det-batch's faces (rects int [N,5], frame first): video frame, face in it."""
+    names, seen = [], {}
+    for fi in rects[:, 0].tolist():
+        j = seen.get(fi, 0)
+        seen[fi] = j + 1
+        names.append(prefix + '%06d_%u.jpg' % (indices[fi], j))
+    return names
+
+
+def _face_path(out_dir, *fn):
+    """Where the stage saves the face file `fn`; without one, the directory of the faces."""
+    return osp.join(out_dir, 'faces', *fn)
+
+
+def _dedupe_nearest(hs, names, hashes, hash_thr):
+    """dupes.nearest_dupes (it appends the kept faces to `hashes`) -> the indices of the faces to keep."""
+    from .dupes import nearest_dupes
+    flags, _ = nearest_dupes(list(zip(hs, names)), hashes, hash_thr)
+    return [i for i, d in enumerate(flags) if not d]
 
 
 # The largest atlas of resized faces process_frames_batch makes for one det-batch: 1 GiB, the
@@ -288,35 +305,25 @@ def _save_batch_device(fr_dev, rects, indices, out_dir, out_prefix, hash_thr, ha
     file names and rectangles only on the host, one D2H of the compressed bytes.  With a store the
     faces' decoded pixels stay in HBM under their files' paths (those with status 0; a det-batch
     that does not fit the store's budget is not stored).  With resize_to the faces are the slots
-    of utils.resize_crops' atlas, which then stands for the frames: slot i with the rectangle
-    (i, 0, 0, w, h) is hashed (the reference hashes the resized face, detection.py:149-153) and
-    encoded."""
-    import os.path as osp
-    from .dupes import ahash_crops, nearest_dupes
-    from .utils import jpeg_encode_crops, resize_crops
-    names, seen = [], {}
-    for fi in rects[:, 0].tolist():
-        j = seen.get(fi, 0)
-        seen[fi] = j + 1
-        names.append(out_prefix + '%06d_%u.jpg' % (indices[fi], j))
+    of utils.resize_crops' atlas, which then stands for the frames: the slots' rectangles
+    (utils.slot_rects) are hashed (as the reference does, detection.py:149-153) and encoded."""
+    from .dupes import ahash_crops
+    from .utils import jpeg_encode_crops, resize_crops, slot_rects
+    names = _face_names(rects, indices, out_prefix)
     if resize_to and names:
         fr_dev, sizes = resize_crops(fr_dev, rects, resize_to)
-        rects = np.zeros((len(names), 5), np.int32)
-        rects[:, 0], rects[:, 3], rects[:, 4] = np.arange(len(names)), sizes[:, 1], sizes[:, 0]
-    keep = list(range(len(names)))
+        rects = slot_rects(sizes)
     if hash_thr and hash_thr != -1 and names:
-        flags, _ = nearest_dupes(list(zip(ahash_crops(fr_dev, rects), names)), hashes, hash_thr)
-        keep = [i for i, d in zip(keep, flags) if not d]
-    names = [names[i] for i in keep]
-    kept = rects[keep]
+        keep = _dedupe_nearest(ahash_crops(fr_dev, rects), names, hashes, hash_thr)
+        names, rects = [names[i] for i in keep], rects[keep]
     if store is None or not names:
-        files = jpeg_encode_crops(fr_dev, kept, 95)
+        files = jpeg_encode_crops(fr_dev, rects, 95)
     else:
-        files, pixels, offsets, status = jpeg_encode_crops(fr_dev, kept, 95, decoded=True)
-        store.add([osp.join(out_dir, 'faces', fn) for fn in names], pixels, offsets,
-                  np.stack([kept[:, 4] - kept[:, 2], kept[:, 3] - kept[:, 1]], 1), status == 0)
+        files, pixels, offsets, status = jpeg_encode_crops(fr_dev, rects, 95, decoded=True)
+        store.add([_face_path(out_dir, fn) for fn in names], pixels, offsets,
+                  np.stack([rects[:, 4] - rects[:, 2], rects[:, 3] - rects[:, 1]], 1), status == 0)
     for fn, data in zip(names, files):
-        with open(osp.join(out_dir, 'faces', fn), 'wb') as f:
+        with open(_face_path(out_dir, fn), 'wb') as f:
             f.write(data)
     return names
 
@@ -326,14 +333,12 @@ def detect_faces(files, model, vid_params, det_params, save_params, hash_thr, jp
     dedupe.  Saving annotated frames / rejects (debug IO) is not mirrored.  jpeg_encoder, store: see
     process_frames_batch; the faces the overall dedupe removes leave the store too."""
     import os
-    import os.path as osp
-    import numpy as np
     from .dupes import remove_dupes_overall, unpack_hash
     from . import _native as nat
     video_step, video_fragment, video_area, video_reader, mjpeg_reader = vid_params
     bs = det_params[0]
     out_dir, out_prefix = save_params[0], save_params[1]
-    os.makedirs(osp.join(out_dir, 'faces'), exist_ok=True)
+    os.makedirs(_face_path(out_dir), exist_ok=True)
     if len(files) > 1:
         print('File count: ' + str(len(files)))
     fnames, hashes_all = [], []
@@ -361,9 +366,9 @@ def detect_faces(files, model, vid_params, det_params, save_params, hash_thr, jp
                                          ('hash', hash_thr, save_params[5], out_dir))
         if store is not None:
             left = set(fnames)
-            store.drop([osp.join(out_dir, 'faces', fn) for fn in before if fn not in left])
-    paths = [osp.join(out_dir, 'faces', fn) for fn in fnames]
+            store.drop([_face_path(out_dir, fn) for fn in before if fn not in left])
+    paths = [_face_path(out_dir, fn) for fn in fnames]
     print()
-    print('Saved a total of %u faces to: %s' % (len(paths), osp.join(out_dir, 'faces')))
+    print('Saved a total of %u faces to: %s' % (len(paths), _face_path(out_dir)))
     print()
     return paths

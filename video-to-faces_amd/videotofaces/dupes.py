@@ -95,13 +95,13 @@ def unpack_hash(h):
 def ahash_crops(frames_dev, crops):
     """dupes.ahash (dupes.py:11-15) of every crop (int [N,5] frame, x1, y1, x2, y2) of the
     CUDA uint8 frames [B,H,W,3] -> uint64 [N] (vtf_ahash_crops)."""
-    c = np.ascontiguousarray(crops, dtype=np.int32).reshape(-1, 5)
+    c = nat.crop_table(crops)
     out = np.zeros(c.shape[0], np.uint64)
     if c.shape[0] == 0:
         return out
-    B, H, W = frames_dev.shape[:3]
-    nat.check(nat.lib().vtf_ahash_crops(nat.ptr(frames_dev), B, H, W, frames_dev.stride(0), frames_dev.stride(1),
-                                        c.ctypes.data, c.shape[0], out.ctypes.data, nat.stream_ptr(frames_dev.device)))
+    frames_dev, fargs = nat.frames_args(frames_dev)
+    nat.check(nat.lib().vtf_ahash_crops(*fargs, c.ctypes.data, c.shape[0], out.ctypes.data,
+                                        nat.stream_ptr(frames_dev.device)))
     return out
 
 

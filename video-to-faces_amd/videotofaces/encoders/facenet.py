@@ -14,6 +14,7 @@ import torch
 
 from .. import _native as nat
 from .. import synth
+from ..utils import pack_atlas, slot_rects
 
 
 class InceptionResnetV1:
@@ -80,37 +81,25 @@ class InceptionResnetV1:
 def blob_from_images(images, size, mean, scale, device):
     """cv2.dnn.blobFromImages(images, scale, (size,size), (mean,)*3, swapRB=True) on device:
     list of uint8 BGR crops -> fp32 [N,3,size,size]."""
-    n = len(images)
-    out = torch.empty((n, 3, size, size), dtype=torch.float32, device=device)
-    if n == 0:
-        return out
-    # pack the crops as 1-row-frame strips of one upload: each crop becomes its own frame
-    Hm = max(im.shape[0] for im in images)
-    Wm = max(im.shape[1] for im in images)
-    buf = np.zeros((n, Hm, Wm, 3), np.uint8)
-    crops = np.zeros((n, 5), np.int32)
-    for i, im in enumerate(images):
-        h, w = im.shape[:2]
-        buf[i, :h, :w] = im
-        crops[i] = (i, 0, 0, w, h)
-    return blob_from_frames(torch.from_numpy(buf).to(device), crops, size, mean, scale)
+    if len(images) == 0:
+        return torch.empty((0, 3, size, size), dtype=torch.float32, device=device)
+    # one upload: each crop becomes its own frame of an atlas
+    buf, sizes = pack_atlas(images)
+    return blob_from_frames(torch.from_numpy(buf).to(device), slot_rects(sizes), size, mean, scale)
 
 
 def blob_from_frames(frames_dev, crops, size, mean, scale):
     """The blob kernel of blob_from_images on frames already in HBM: CUDA uint8 BGR [F,H,W,3] and
     host int crops [N,5] (frame, x1, y1, x2, y2) -> fp32 [N,3,size,size]."""
+    frames_dev, fargs = nat.frames_args(frames_dev)
     device = frames_dev.device
-    crops = np.ascontiguousarray(crops, np.int32).reshape(-1, 5)
+    crops = nat.crop_table(crops)
     n = crops.shape[0]
     out = torch.empty((n, 3, size, size), dtype=torch.float32, device=device)
     if n == 0:
         return out
-    if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
-        frames_dev = frames_dev.contiguous()
-    F, H, W = frames_dev.shape[:3]
     dc = torch.from_numpy(crops).to(device)
-    nat.check(nat.lib().vtf_blob_from_crops(nat.ptr(frames_dev), F, H, W, frames_dev.stride(0), frames_dev.stride(1),
-                                            nat.ptr(dc), n, size, ctypes.c_float(mean), ctypes.c_float(scale),
+    nat.check(nat.lib().vtf_blob_from_crops(*fargs, nat.ptr(dc), n, size, ctypes.c_float(mean), ctypes.c_float(scale),
                                             nat.ptr(out), nat.stream_ptr(device)))
     return out
 

@@ -6,6 +6,7 @@ scores per k on the GPU (videotofaces.kmeans.Grouper, sklearn-faithful); under
 torch.distributed the k sweep is sharded across ranks and the per-k labels
 and scores are all-gathered.
 """
+import collections
 import math
 import os
 import os.path as osp
@@ -15,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from . import utils
 from .dupes import remove_dupes_overall  # noqa: F401  (re-export like the reference)
 
 
@@ -50,30 +52,25 @@ DECODE_MAX_SIDE = 1024
 
 def _area_rect(h, w, area):
     """crop_to_area's slice of an h x w image as (x1, y1, x2, y2), clipped as numpy clips it."""
-    if not area:
-        return 0, 0, w, h
     px1, py1, px2, py2 = area
     x1, x2, _ = slice(int(px1 * w), int(px2 * w + 1)).indices(w)
     y1, y2, _ = slice(int(py1 * h), int(py2 * h + 1)).indices(h)
     return x1, y1, max(x1, x2), max(y1, y2)
 
 
-def _decode_group(paths, at):
-    """The next group of files from paths[at:] -> (files, probed, host, hm, wm): the files' bytes,
-    their probed (h, w, kind), the images already read on the host {index: BGR array} (files the
-    device does not decode, and oversize ones) and the atlas size.  A group ends at DECODE_GROUP
-    files or before the file that would take the atlas past DECODE_ATLAS_BYTES; a file with a side
-    above DECODE_MAX_SIDE is a group of its own.  Never empty."""
-    return _next_group(paths, at, None, 'device')[:5]
+# The files of one atlas, by their index in the group: `files` their bytes (None for a path not read
+# as bytes), `probed` their (h, w, kind), `host` {index: BGR array} the images already read on the
+# host, `stored` {index: the store's (chunk, byte offset, h, w)}, (hm, wm) the atlas size.
+_Group = collections.namedtuple('_Group', 'files probed host stored hm wm')
 
 
 def _next_group(paths, at, store, decoder):
-    """_decode_group with a face store: -> (files, probed, host, hm, wm, stored).  A path the store
-    holds is not opened: stored[index] is the store's (chunk, byte offset, h, w), its entry in
-    `files` is None and its size is the store's.  Any other path goes the way `decoder` says: read
-    and probed for 'device' as in _decode_group, read with _imread into `host` for 'host' (entry
-    None in `files`).  The group rules are the same for all of them."""
-    from .utils import jpeg_probe
+    """The next group of files from paths[at:] -> _Group, never empty.  A path the store holds is not
+    opened: it is in `stored` and its size is the store's.  Any other path goes the way `decoder`
+    says.  'device': read and probed; a file the device does not decode, or one with a side above
+    DECODE_MAX_SIDE, is read with _imread into `host` as well.  'host': read with _imread into
+    `host` only.  A group ends at DECODE_GROUP files or before the file that would take the atlas
+    past DECODE_ATLAS_BYTES; a file with a side above DECODE_MAX_SIDE is a group of its own."""
     files, probed, host, stored, hm, wm = [], [], {}, {}, 1, 1
     while at + len(files) < len(paths) and len(files) < DECODE_GROUP:
         i = len(files)
@@ -84,7 +81,7 @@ def _next_group(paths, at, store, decoder):
         elif decoder == 'device':
             with open(paths[at + i], 'rb') as f:
                 data = f.read()
-            h, w, kind = jpeg_probe(data)
+            h, w, kind = utils.jpeg_probe(data)
             if kind != 0 or max(h, w) > DECODE_MAX_SIDE:
                 img = _imread(paths[at + i])  # (fails here as it fails on the host path)
                 h, w = img.shape[:2]
@@ -103,43 +100,60 @@ def _next_group(paths, at, store, decoder):
         hm, wm = max(hm, h), max(wm, w)
         if big:
             break
-    return files, probed, host, hm, wm, stored
+    return _Group(files, probed, host, stored, hm, wm)
 
 
-def _gather_group(files, probed, host, hm, wm, stored, decoder, dev):
-    """The atlas of a group that has stored faces (or host-read files only): the stored faces by
-    one utils.faces_to_atlas launch, the files `decoder` = 'device' read by utils.jpeg_decode and
-    slot by slot into the same atlas.  -> (atlas, sizes, status) as utils.jpeg_decode gives them;
-    the slots of `host` are left for the caller."""
-    from .utils import faces_to_atlas, jpeg_decode
+def _group_atlas(group, paths, at, decoder, dev):
+    """The atlas of the group at paths[at:] with every slot filled -> (atlas CUDA uint8 [n,H,W,3],
+    sizes int32 [n,2] (h, w)).  One host-read file (an oversize one): its pixels are the atlas.
+    Stored faces, or files `decoder` = 'host' read: one utils.faces_to_atlas launch makes the atlas
+    and fills the stored faces' slots; the files that are neither are decoded by one
+    utils.jpeg_decode call and copied slot by slot.  Otherwise one utils.jpeg_decode call over all
+    files makes the atlas.  The host-read images go into their slots last; a file whose scan turns
+    out to be damaged is read with _imread then and joins `group.host`, which is updated in place."""
+    files, probed, host, stored = group.files, group.probed, group.host, group.stored
     n = len(files)
-    sizes, status = np.array([p[:2] for p in probed], np.int32).reshape(-1, 2), np.zeros(n, np.int32)
-    faces = [None] * n
-    for i, (chunk, off, h, w) in stored.items():
-        faces[i] = chunk[off:off + h * w * 3]
-    atlas = faces_to_atlas(faces, sizes, hm, wm, dev)
-    rest = [i for i in range(n) if i not in stored and i not in host]
-    if rest:
-        sub, ssz, sst = jpeg_decode([files[i] for i in rest], dev, probed=[probed[i] for i in rest])
-        for j, i in enumerate(rest):
-            status[i] = sst[j]
-            if sst[j] == 0:
-                h, w = int(ssz[j, 0]), int(ssz[j, 1])
-                atlas[i, :h, :w] = sub[j, :h, :w]
-    return atlas, sizes, status
+    if n == 1 and host:
+        atlas = torch.from_numpy(np.ascontiguousarray(host[0])[None]).to(dev)
+        return atlas, np.array([host[0].shape[:2]], np.int32)
+    if stored or decoder != 'device':
+        sizes, status = np.array([p[:2] for p in probed], np.int32).reshape(-1, 2), np.zeros(n, np.int32)
+        faces = [None] * n
+        for i, (chunk, off, h, w) in stored.items():
+            faces[i] = chunk[off:off + h * w * 3]
+        atlas = utils.faces_to_atlas(faces, sizes, group.hm, group.wm, dev)
+        rest = [i for i in range(n) if i not in stored and i not in host]
+        if rest:
+            sub, ssz, sst = utils.jpeg_decode([files[i] for i in rest], dev, probed=[probed[i] for i in rest])
+            for j, i in enumerate(rest):
+                status[i] = sst[j]
+                if sst[j] == 0:
+                    h, w = int(ssz[j, 0]), int(ssz[j, 1])
+                    atlas[i, :h, :w] = sub[j, :h, :w]
+    else:
+        atlas, sizes, status = utils.jpeg_decode(files, dev, probed=probed, min_size=(group.hm, group.wm))
+    for i in np.flatnonzero(status != 0).tolist():
+        if i not in host:  # the scan turned out to be damaged
+            host[i] = _imread(paths[at + i])
+    for i, img in host.items():
+        h, w = img.shape[:2]
+        if h > atlas.shape[1] or w > atlas.shape[2]:  # (a reader that disagrees with the frame header)
+            grown = torch.zeros((n, max(h, atlas.shape[1]), max(w, atlas.shape[2]), 3),
+                                dtype=torch.uint8, device=dev)
+            grown[:, :atlas.shape[1], :atlas.shape[2]] = atlas
+            atlas = grown
+        atlas[i, :h, :w] = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+        sizes[i] = (h, w)
+    return atlas, sizes
 
 
-def _encode_faces_device(paths, model, bs, area, store=None, decoder='device'):
-    """encode_faces with the files decoded on the GPU (utils.jpeg_decode).  The files are decoded in
-    groups (_decode_group), whatever `bs` is; every group's blobs come from the blob kernel
-    model(images) runs, and the forward runs on the same batches of `bs` blobs in the same order, so
-    the embeddings are the host path's bits.  A file the device does not decode (progressive,
-    grayscale, corrupt, ...) or one with a side above DECODE_MAX_SIDE is read with _imread as on the
-    host path and copied into its slot of the group's one atlas.
-    store (a facestore.FaceStore): a path it holds is not opened at all; its decoded pixels are in
-    HBM already and go into its slot by utils.faces_to_atlas.  The other paths of such a run go the
-    way `decoder` says ('host': _imread, 'device': as above), into their slots of the same atlas."""
-    from .utils import jpeg_decode
+def _encode_faces_device(paths, model, bs, area, store, decoder):
+    """encode_faces with the faces' pixels gathered in HBM, in groups that share an atlas
+    (_next_group, _group_atlas), whatever `bs` is: taken from `store` (a facestore.FaceStore or
+    None) where it holds the path, else decoded on the GPU (decoder='device'; a file the device does
+    not decode is read with _imread) or read with _imread ('host').  Every group's blobs come from
+    the blob kernel model(images) runs, and the forward runs on the same batches of `bs` blobs in
+    the same order, so the embeddings are the host path's bits."""
     dev = nat.device_of(model)
     x, pending = [], None  # blobs that wait for a full batch
 
@@ -152,29 +166,12 @@ def _encode_faces_device(paths, model, bs, area, store=None, decoder='device'):
 
     at = 0
     while at < len(paths):
-        files, probed, host, hm, wm, stored = _next_group(paths, at, store, decoder)
-        if len(files) == 1 and host:  # one host-decoded file (an oversize one): its pixels are the atlas
-            atlas = torch.from_numpy(np.ascontiguousarray(host[0])[None]).to(dev)
-            sizes, status, host = np.array([host[0].shape[:2]], np.int32), np.zeros(1, np.int32), {}
-        elif stored or decoder != 'device':
-            atlas, sizes, status = _gather_group(files, probed, host, hm, wm, stored, decoder, dev)
-        else:
-            atlas, sizes, status = jpeg_decode(files, dev, probed=probed, min_size=(hm, wm))
-        for i in np.flatnonzero(status != 0):
-            if int(i) not in host:  # the scan turned out to be damaged
-                host[int(i)] = _imread(paths[at + int(i)])
-        for i, img in host.items():
-            h, w = img.shape[:2]
-            if h > atlas.shape[1] or w > atlas.shape[2]:  # (a reader that disagrees with the frame header)
-                grown = torch.zeros((len(files), max(h, atlas.shape[1]), max(w, atlas.shape[2]), 3),
-                                    dtype=torch.uint8, device=dev)
-                grown[:, :atlas.shape[1], :atlas.shape[2]] = atlas
-                atlas = grown
-            atlas[i, :h, :w] = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
-            sizes[i] = (h, w)
-        crops = np.array([(i,) + _area_rect(int(sizes[i, 0]), int(sizes[i, 1]), area) for i in range(len(files))],
-                         np.int32).reshape(-1, 5)
-        at += len(files)
+        group = _next_group(paths, at, store, decoder)
+        atlas, sizes = _group_atlas(group, paths, at, decoder, dev)
+        crops = utils.slot_rects(sizes)
+        if area:
+            crops[:, 1:] = [_area_rect(int(h), int(w), area) for h, w in sizes]
+        at += len(group.files)
         flush(model.blob_from_frames(atlas, crops), at >= len(paths))
     return np.concatenate(x)
 
@@ -186,21 +183,18 @@ def encode_faces(paths, model, bs, area, jpeg_decoder='host', store=None):
     facestore.FaceStore the detection stage filled): the faces it holds are taken from HBM and their
     files are not opened; the rest go the way jpeg_decoder says.  The same embeddings again."""
     from .facestore import FaceStore
-    from .utils import crop_to_area
     if jpeg_decoder not in ('host', 'device'):
         raise ValueError("jpeg_decoder must be 'host' or 'device'")
     if store is not None and not isinstance(store, FaceStore):
         raise ValueError('store must be a FaceStore or None')
     print('Extracting features from images for grouping')
-    if store is not None and len(paths):
+    if len(paths) and (store is not None or jpeg_decoder == 'device'):
         return _encode_faces_device(paths, model, bs, area, store, jpeg_decoder)
-    if jpeg_decoder == 'device' and len(paths):
-        return _encode_faces_device(paths, model, bs, area)
     x = []
     for bn in range(math.ceil(len(paths) / bs)):
         images = [_imread(p) for p in paths[bs * bn:bs * (bn + 1)]]
         if area:
-            images = [crop_to_area(img, area) for img in images]
+            images = [utils.crop_to_area(img, area) for img in images]
         x.append(model(images))
     return np.concatenate(x)
 

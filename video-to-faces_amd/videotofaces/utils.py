@@ -1,5 +1,7 @@
 """Small host helpers (src/videotofaces/utils/image.py)."""
 
+import numpy as np
+
 
 def crop_to_area(img, area):
     """utils/image.py:17-22"""
@@ -46,7 +48,6 @@ def resize_sizes(hw, to_area, upscale=True):
 
 
 def _lin_coefs(src, dst):
-    import numpy as np
     d = np.arange(dst, dtype=np.float64)
     f = ((d + 0.5) * (1.0 / (dst / src)) - 0.5).astype(np.float32)
     s = np.floor(f).astype(np.int64)
@@ -62,7 +63,6 @@ def _lin_coefs(src, dst):
 
 def resize_linear(img, H, W):
     """OpenCV uint8 INTER_LINEAR resize of an HxWx3 image (the kernels' lin_coef arithmetic)."""
-    import numpy as np
     h, w = img.shape[:2]
     if (h, w) == (H, W):
         return img.copy()
@@ -91,6 +91,25 @@ def imwrite(path, img):
         return True
 
 
+def slot_rects(sizes):
+    """Slot i of an atlas [N,Hmax,Wmax,3] as the crop rectangle (i, 0, 0, w, h), with which the atlas
+    stands for the frames of a kernel that reads crops: sizes int [N,2] (h, w) -> int32 [N,5]."""
+    sizes = np.asarray(sizes, np.int32).reshape(-1, 2)
+    rects = np.zeros((len(sizes), 5), np.int32)
+    rects[:, 0], rects[:, 3], rects[:, 4] = np.arange(len(sizes)), sizes[:, 1], sizes[:, 0]
+    return rects
+
+
+def pack_atlas(images):
+    """A non-empty list of uint8 [h,w,3] images as a host atlas -> (uint8 [N,Hmax,Wmax,3] with image
+    i in atlas[i, :h, :w] and zeros around it, sizes int32 [N,2] (h, w))."""
+    sizes = np.array([im.shape[:2] for im in images], np.int32).reshape(-1, 2)
+    atlas = np.zeros((len(images), int(sizes[:, 0].max()), int(sizes[:, 1].max()), 3), np.uint8)
+    for i, im in enumerate(images):
+        atlas[i, :im.shape[0], :im.shape[1]] = im
+    return atlas, sizes
+
+
 def jpeg_encode_crops(frames_dev, crops, quality=95, decoded=False):
     """cv2.imwrite of every crop (int [N,5] frame, x1, y1, x2, y2) of the CUDA uint8 BGR frames
     [B,H,W,3] on the device (vtf_jpeg_encode_crops) -> list of N `bytes`, each a whole baseline
@@ -102,24 +121,18 @@ def jpeg_encode_crops(frames_dev, crops, quality=95, decoded=False):
     with crop i's BGR [h][w][3] at pixels[offsets[i]:offsets[i+1]] (offsets np.int64 [N+1]), status
     np.int32 [N]: 0, or 2 for a crop whose pixels are not valid (never for 8-bit frames)."""
     import ctypes
-    import numpy as np
     import torch
     from . import _native as nat
-    if not (isinstance(frames_dev, torch.Tensor) and frames_dev.is_cuda and frames_dev.dtype == torch.uint8
-            and frames_dev.dim() == 4 and frames_dev.shape[3] == 3):
-        raise ValueError('frames must be a CUDA uint8 tensor [B,H,W,3]')
+    frames_dev, fargs = nat.frames_args(frames_dev)
     if not isinstance(decoded, bool):
         raise ValueError('decoded must be True or False')
-    crops = np.ascontiguousarray(np.asarray(crops, np.int32).reshape(-1, 5))
+    crops = nat.crop_table(crops)
     n = crops.shape[0]
     dev = frames_dev.device
     if n == 0:
         if decoded:
             return [], torch.empty(0, dtype=torch.uint8, device=dev), np.zeros(1, np.int64), np.zeros(0, np.int32)
         return []
-    if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
-        frames_dev = frames_dev.contiguous()
-    B, H, W = frames_dev.shape[:3]
     offs = np.zeros(n + 1, np.int64)
     total = ctypes.c_int64(0)
     # first guess: the header and a byte per pixel (quality 95 photographs need about half that)
@@ -132,8 +145,8 @@ def jpeg_encode_crops(frames_dev, crops, quality=95, decoded=False):
         pixels = torch.empty(int(poffs[n]), dtype=torch.uint8, device=dev) if decoded else None
         for attempt in (0, 1):
             out = torch.empty(cap, dtype=torch.uint8, device=dev)
-            args = (nat.ptr(frames_dev), B, H, W, frames_dev.stride(0), frames_dev.stride(1), crops.ctypes.data, n,
-                    int(quality), nat.ptr(out), cap, offs.ctypes.data, ctypes.byref(total))
+            args = (*fargs, crops.ctypes.data, n, int(quality), nat.ptr(out), cap, offs.ctypes.data,
+                    ctypes.byref(total))
             if decoded:
                 rc = nat.lib().vtf_jpeg_encode_crops_decoded(*args, nat.ptr(pixels), pixels.numel(),
                                                              status.ctypes.data, nat.stream_ptr(dev))
@@ -155,7 +168,6 @@ def faces_to_atlas(faces, sizes, hm, wm, device):
     atlas[i, :h, :w]; the rest of a slot, and the whole slot of a None entry, is not written (the
     caller fills it).  One launch for all faces."""
     import ctypes
-    import numpy as np
     import torch
     from . import _native as nat
     dev = nat.require_gpu(device)
@@ -187,10 +199,9 @@ def resize_crops(frames_dev, crops, to_area, upscale=True):
     uint8 tensor [N,Hmax,Wmax,3] with the resized crop i in atlas[i, :h, :w] (the rest of a slot
     is not written), and np.int32 [N,2] (h, w) = resize_sizes of the crops; Hmax / Wmax are the
     largest h / w.  The pixels are resize_linear's, bit for bit.  The atlas with the rectangles
-    (i, 0, 0, w, h) is an input of dupes.ahash_crops and jpeg_encode_crops.  to_area: a positive
+    slot_rects(sizes) is an input of dupes.ahash_crops and jpeg_encode_crops.  to_area: a positive
     int or a pair of positive ints (aw, ah).  One library call, no copy to the host.  A crop whose
     destination has a zero side (a 1 x 500 crop to 100) raises ValueError."""
-    import numpy as np
     import torch
     from . import _native as nat
 
@@ -200,7 +211,7 @@ def resize_crops(frames_dev, crops, to_area, upscale=True):
         raise ValueError('to_area must be a positive int or a pair of positive ints (aw, ah)')
     if not isinstance(upscale, bool):
         raise ValueError('upscale must be True or False')
-    crops = np.ascontiguousarray(np.asarray(crops, np.int32).reshape(-1, 5))
+    crops = nat.crop_table(crops)
     n = crops.shape[0]
     src = np.stack([crops[:, 4] - crops[:, 2], crops[:, 3] - crops[:, 1]], 1)
     if (src < 1).any():
@@ -209,20 +220,14 @@ def resize_crops(frames_dev, crops, to_area, upscale=True):
     if (sizes < 1).any():
         i = int(np.nonzero((sizes < 1).any(1))[0][0])
         raise ValueError('crop %d (%d x %d) resized to %s has a zero side' % (i, src[i, 0], src[i, 1], to_area))
-    if not (isinstance(frames_dev, torch.Tensor) and frames_dev.is_cuda and frames_dev.dtype == torch.uint8
-            and frames_dev.dim() == 4 and frames_dev.shape[3] == 3):
-        raise ValueError('frames must be a CUDA uint8 tensor [B,H,W,3]')
+    frames_dev, fargs = nat.frames_args(frames_dev)
     dev = frames_dev.device
     if n == 0:
         return torch.empty((0, 1, 1, 3), dtype=torch.uint8, device=dev), sizes
-    if frames_dev.stride(3) != 1 or frames_dev.stride(2) != 3:
-        frames_dev = frames_dev.contiguous()
-    B, H, W = frames_dev.shape[:3]
     hm, wm = int(sizes[:, 0].max()), int(sizes[:, 1].max())
     with torch.cuda.device(dev):
         atlas = torch.empty((n, hm, wm, 3), dtype=torch.uint8, device=dev)
-        nat.check(nat.lib().vtf_resize_crops(nat.ptr(frames_dev), B, H, W, frames_dev.stride(0), frames_dev.stride(1),
-                                             crops.ctypes.data, sizes.ctypes.data, n, nat.ptr(atlas), hm, wm,
+        nat.check(nat.lib().vtf_resize_crops(*fargs, crops.ctypes.data, sizes.ctypes.data, n, nat.ptr(atlas), hm, wm,
                                              atlas.stride(0), atlas.stride(1), nat.stream_ptr(dev)))
     return atlas, sizes
 
@@ -231,7 +236,6 @@ def jpeg_probe(data):
     """Headers of one JPEG file (`bytes`) parsed on the host (vtf_jpeg_probe, no GPU) ->
     (h, w, kind): kind 0 = decodable on the device (baseline 4:2:0), 1 = another JPEG,
     2 = not a JPEG or truncated headers."""
-    import numpy as np
     from . import _native as nat
     info = np.zeros(8, np.int32)
     buf = np.frombuffer(data, np.uint8)
@@ -239,40 +243,50 @@ def jpeg_probe(data):
     return int(info[0]), int(info[1]), int(info[2])
 
 
-def jpeg_decode(files, device=None, probed=None, min_size=(1, 1), scan='serial', seg_bytes=0):
+def jpeg_decode(files, device=None, probed=None, min_size=(1, 1), scan='serial', seg_bytes=0, out=None):
     """cv2.imread of every file (a list of `bytes`, each a whole JPEG file) on the device
     (vtf_jpeg_decode) -> (atlas, sizes, status): a CUDA uint8 BGR tensor [N,Hmax,Wmax,3] with file
     i in atlas[i, :h, :w] (the rest of a slot is not written), np.int32 [N,2] (h, w) and np.int32
     [N]: 0 decoded, 1 a JPEG the device does not decode (anything but baseline 4:2:0; slot
-    untouched), 2 corrupt or no JPEG (slot zeroed), 3 too large (never here: the atlas is sized
-    from the probed headers).  The pixels are libjpeg's, bit for bit.  The headers are probed on
+    untouched), 2 corrupt or no JPEG (slot zeroed), 3 too large (only with out=: the atlas made here
+    is sized from the probed headers).  The pixels are libjpeg's, bit for bit.  The headers are probed on
     the host to size the atlas; then one library call and one H2D copy of the compressed bytes.
     probed: jpeg_probe's (h, w, kind) of every file when the caller has them already.  min_size:
     (Hmax, Wmax) is at least this, for slots the caller fills itself (files with status != 0).
     scan: 'serial' decodes a file's scan with one lane (many small files per call: face crops),
     'split' with the lanes of a workgroup, each on a segment of seg_bytes of the scan
     (vtf_jpeg_decode_split: large files, video frames; seg_bytes 0 = the library's default,
-    otherwise a multiple of 4 in [4, 4096]).  The same atlas, sizes and statuses either way."""
-    import numpy as np
+    otherwise a multiple of 4 in [4, 4096]).  The same atlas, sizes and statuses either way.
+    out: a CUDA uint8 tensor [N,H,W,3] to decode into, on its device (`device`, when given, must be
+    that one), instead of a new atlas.  No header is then probed here: a file larger than a slot
+    gets status 3 (ValueError where `probed` says so)."""
     import torch
     from . import _native as nat
     if scan not in ('serial', 'split'):
         raise ValueError("scan must be 'serial' or 'split'")
-    dev = nat.require_gpu(device)
     n = len(files)
     sizes, status = np.zeros((n, 2), np.int32), np.zeros(n, np.int32)
-    if probed is None:
-        probed = [jpeg_probe(f) for f in files]
-    hm, wm = max(1, int(min_size[0])), max(1, int(min_size[1]))
-    for h, w, kind in probed:
-        if kind == 0:
-            hm, wm = max(hm, h), max(wm, w)
-    atlas = torch.empty((n, hm, wm, 3), dtype=torch.uint8, device=dev)
+    if out is None:
+        dev = nat.require_gpu(device)
+        if probed is None:
+            probed = [jpeg_probe(f) for f in files]
+        hm, wm = max(1, int(min_size[0])), max(1, int(min_size[1]))
+        for h, w, kind in probed:
+            if kind == 0:
+                hm, wm = max(hm, h), max(wm, w)
+        atlas = torch.empty((n, hm, wm, 3), dtype=torch.uint8, device=dev)
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 4
+                and out.shape[0] == n and out.shape[3] == 3 and out.stride(3) == 1 and out.stride(2) == 3):
+            raise ValueError('out must be a CUDA uint8 tensor [N,H,W,3] with packed pixels and a slot for every file')
+        dev, atlas, hm, wm = out.device, out, out.shape[1], out.shape[2]
+        if device is not None and torch.device(device) not in (dev, torch.device(dev.type)):
+            raise ValueError('out is on %s, not on %s' % (dev, device))
+        if any(kind == 0 and (h > hm or w > wm) for h, w, kind in probed or ()):
+            raise ValueError('out is smaller than a file')
     if n == 0:
         return atlas, sizes, status
-    offs = np.zeros(n + 1, np.int64)
-    np.cumsum([len(f) for f in files], out=offs[1:])
-    data = np.frombuffer(b''.join(files) or b'\0', np.uint8)
+    data, offs = nat.file_table(files)
     with torch.cuda.device(dev):
         args = (data.ctypes.data, offs.ctypes.data, n, nat.ptr(atlas), hm, wm, atlas.stride(0), atlas.stride(1),
                 sizes.ctypes.data, status.ctypes.data)

@@ -407,21 +407,24 @@ class MJPEGReader:
             img = np.asarray(Image.open(io.BytesIO(data)).convert('RGB'))
         except Exception as e:
             raise ValueError('%s: frame %d does not decode: %s' % (self.path, i, e))
-        if img.shape[:2] != (self.height, self.width):
-            raise ValueError('%s: frame %d is %d x %d, the first frame %d x %d'
-                             % (self.path, i, img.shape[1], img.shape[0], self.width, self.height))
+        self._check_size(i, *img.shape[:2])
         return img[:, :, ::-1]
+
+    def _check_size(self, i, h, w):
+        if (h, w) != (self.height, self.width):
+            raise ValueError('%s: frame %d is %d x %d, the first frame %d x %d'
+                             % (self.path, i, w, h, self.width, self.height))
 
     def read(self, indices, device=None, decoder='device', seg_bytes=0):
         """BGR frames [B,H,W,3] uint8 in HBM of `device` (default cuda:0).  decoder='device': the
-        frames' compressed bytes go to vtf_jpeg_decode_split in one call, which decodes them
-        straight into the result (its slots are the frames); a frame the device does not decode
+        frames' compressed bytes go to utils.jpeg_decode(scan='split', out=) in one call, which decodes
+        them straight into the result (its slots are the frames); a frame the device does not decode
         (4:4:4 / 4:2:2 sampling, restart intervals, no DHT segment, progressive, a corrupt scan) is
         decoded with Pillow on the host and copied into its slot: the same pixels either way.
         decoder='host' decodes every frame with Pillow and uploads the pixels.  Indices may repeat
         and come in any order.  A frame of another size than the first is a ValueError."""
         import torch
-        from . import _native as nat
+        from . import _native as nat, utils
         if decoder not in ('device', 'host'):
             raise ValueError("decoder must be 'device' or 'host'")
         dev = nat.require_gpu(device)
@@ -443,19 +446,11 @@ class MJPEGReader:
             host = np.stack([self._host_frame(i, f) for i, f in zip(order, files)])
             out.copy_(torch.from_numpy(host))
         else:
-            sizes, status = np.zeros((n, 2), np.int32), np.zeros(n, np.int32)
-            offs = np.zeros(n + 1, np.int64)
-            np.cumsum([len(f) for f in files], out=offs[1:])
-            data = np.frombuffer(b''.join(files), np.uint8)
-            with torch.cuda.device(dev):
-                nat.check(nat.lib().vtf_jpeg_decode_split(data.ctypes.data, offs.ctypes.data, n, nat.ptr(out), H, W,
-                                                          out.stride(0), out.stride(1), sizes.ctypes.data,
-                                                          status.ctypes.data, int(seg_bytes), nat.stream_ptr(dev)))
+            _, sizes, status = utils.jpeg_decode(files, dev, scan='split', seg_bytes=seg_bytes, out=out)
             for k in range(n):
-                if status[k] == 0 and (int(sizes[k, 0]), int(sizes[k, 1])) != (H, W):
-                    raise ValueError('%s: frame %d is %d x %d, the first frame %d x %d'
-                                     % (self.path, order[k], sizes[k, 1], sizes[k, 0], W, H))
-                if status[k] != 0:
+                if status[k] == 0:
+                    self._check_size(order[k], int(sizes[k, 0]), int(sizes[k, 1]))
+                else:
                     out[k].copy_(torch.from_numpy(np.ascontiguousarray(self._host_frame(order[k], files[k]))))
         if n == idx.size and np.array_equal(inv, np.arange(n)):
             return out
