@@ -91,6 +91,11 @@ int vtf_mtcnn_stats(vtf_mtcnn_t h, int64_t* out8);
  * nonzero() order (mtcnn.py:183-186) -- are copied to out (up to cap) and their count to *out_n. */
 int vtf_mtcnn_stage1_keys(vtf_mtcnn_t h, int enable, uint64_t* out, int64_t cap, int64_t* out_n);
 
+/* Parity introspection (tests): the last detect call's PNet plan (pnet_exact_tiles) -- per pyramid
+ * level 1 if the exact-levels kernel is planned to take it (the launch still falls back to the
+ * general kernel on VTF_PNET_X=0), else 0 -- copied to out (up to cap), the level count to *out_n. */
+int vtf_mtcnn_pnet_plan(vtf_mtcnn_t h, int32_t* out, int64_t cap, int64_t* out_n);
+
 /* Kernel timing of the dominant kernel (fused pyramid+PNet) with HIP events recorded on the
  * handle's stream around each launch.  enable=1 resets and starts accumulating; the call
  * returns the totals so far: elapsed ms, launches, algorithmic FLOPs (2*MAC of conv1-3 and

@@ -601,6 +601,36 @@ __device__ inline uint2 patch_bytes8(__amdgpu_buffer_rsrc_t rsrc, int i0, int w,
     return make_uint2(v[0], v[1]);
 }
 
+// pixels [p0, p0 + 3) of a frame patch of w-pixel rows (nrows of them) at row stride rs, read
+// through a buffer descriptor over the patch's byte extent (pixels past the patch read 0), each
+// packed B | G << 8 | R << 16: the exact-levels variant's staging and prefetch granule
+constexpr int PX_PER = 3, PX_ROUND = 256 * PX_PER;  // pixels per thread / per workgroup round
+__device__ inline void patch_px3(__amdgpu_buffer_rsrc_t rsrc, int p0, int w, int nrows, int rs, uint32_t v[PX_PER]) {
+    int r = udiv_est(p0, w), c = p0 - r * w;
+#pragma unroll
+    for (int j = 0; j < PX_PER; j++) {
+        // (rows past the patch lie past the extent: clamped so the offset stays in range)
+        const int off = min(r, nrows) * rs + c * 3;
+        v[j] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, off, 0, 0) |
+               (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, off + 1, 0, 0) << 8 |
+               (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, off + 2, 0, 0) << 16;
+        if (++c == w) c = 0, r++;
+    }
+}
+
+// a packed frame pixel as the fp16 pixel [2R - 255, 2G - 255, 2B - 255, 0] (odd integers of
+// magnitude <= 255: exact), the one-pass exact fill's patch format
+typedef __attribute__((ext_vector_type(4))) _Float16 f16px;
+__device__ inline f16px px_f16(uint32_t v) {
+    // 0x6000 | c << 1 is the half 512 + c (ulp 1/2 there), and 2 (512 + c) - 1279 = 2 c - 255 is
+    // one exact fma; the fourth half is 512 * 0 + 0
+    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+    const u32x2 w = {((v >> 15) & 0x1feu) | ((v & 0xff00u) << 9) | 0x60006000u, ((v & 0xffu) << 1) | 0x60006000u};
+    const f16px k2 = {(_Float16)2.f, (_Float16)2.f, (_Float16)2.f, (_Float16)0.f};
+    const f16px kb = {(_Float16)-1279.f, (_Float16)-1279.f, (_Float16)-1279.f, (_Float16)0.f};
+    return __builtin_elementwise_fma(__builtin_bit_cast(f16px, w), k2, kb);
+}
+
 constexpr int PNET_TILE_CHUNK = 4;  // default tiles per atomic chunk (VTF_PNET_CHUNK)
 constexpr int PNET_GROUPS_PER_CU = (160 * 1024) / ((PNET_LDS + 511) / 512 * 512);  // LDS granule: 512 B
 static_assert(PNET_GROUPS_PER_CU >= 2, "k_pnet tile too large for 2 workgroups per CU");
@@ -696,9 +726,13 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
     //  taking an exec-skip branch per mark)
     auto mark = [&](int k) {
         if (__builtin_expect(clk_on, 0) && tid == 0) {
+            // (index laundered: the LDS addresses are formed here, not hoisted out of the tile loop
+            //  into a register that lives, or spills, across it)
+            int kk = k, zz = 0;
+            asm volatile("" : "+v"(kk), "+v"(zz));
             const unsigned long long t = clock64();
-            s_clk[k] += t - s_tlast;
-            s_tlast = t;
+            s_clk[kk] += t - (&s_tlast)[zz];
+            (&s_tlast)[zz] = t;
         }
     };
     if (tid < 8) s_clk[tid] = 0;
@@ -797,14 +831,33 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
             fx1 = xbin[rx].y;
         }
         const int pw3 = (fx1 - fx0) * 3;
-        const bool staged = !P.pre && (int64_t)(fy1 - fy0) * pw3 <= LP::PATCH;
+        // (X) one-pass fill: the patch is staged as fp16 pixels, 8 bytes each (pnet_exact_tiles:
+        // it fits on every exact level); the other variants stage the packed BGR bytes
+        constexpr bool px = X;
+        const int npx = (fy1 - fy0) * (fx1 - fx0);
+        const bool staged = !P.pre && (px ? (int64_t)npx * 8 : (int64_t)(fy1 - fy0) * pw3) <= LP::PATCH;
         uint8_t* patch = (uint8_t*)sP;
         // (gathers below issue 8 loads per thread before the first use: latency-bound otherwise)
         // (nothing left to stage -- the whole patch came with the previous tile's prefetch, the
         //  common case on the upsampled levels -- needs no barrier: block-uniform condition)
-        const bool stage_more = staged && !(o.dbg & 64) && (fy1 - fy0) * pw3 > (pf_done ? 256 * 8 : 0);
-        if (stage_more) {
-            // 8 consecutive patch bytes per thread (one 8-byte LDS store); the first 2 KB were
+        // (X: the prefetch covers the patch's first PX_ROUND pixels)
+        constexpr int PF_BYTES = X ? PX_ROUND * 3 : 256 * 8;
+        const bool stage_more = staged && !(o.dbg & 64) && (fy1 - fy0) * pw3 > (pf_done ? PF_BYTES : 0);
+        if (stage_more && px) {
+            // PX_PER consecutive pixels per thread, converted in registers (one 8-byte LDS store each)
+            const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(fr + (int64_t)fy0 * row_stride + fx0 * 3), 0, (int)((fy1 - fy0 - 1) * (int)row_stride + pw3),
+                0x00020000);
+            for (int p0 = PX_PER * tid + (pf_done ? PX_ROUND : 0); p0 < npx; p0 += PX_ROUND) {
+                uint32_t v[PX_PER];
+                patch_px3(rs_src, p0, fx1 - fx0, fy1 - fy0, (int)row_stride, v);
+#pragma unroll
+                for (int j = 0; j < PX_PER; j++)
+                    if (p0 + j < npx) ((f16px*)patch)[p0 + j] = px_f16(v[j]);
+            }
+            __syncthreads();
+        } else if (stage_more) {
+            // 8 consecutive patch bytes per thread (one 8-byte LDS store); the first PF_BYTES were
             // prefetched during the previous tile when pf_done
             const int nbytes = (fy1 - fy0) * pw3;
             const uint8_t* src = fr + (int64_t)fy0 * row_stride + fx0 * 3;
@@ -812,7 +865,7 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
                 (void*)src, 0, (int)((fy1 - fy0 - 1) * (int)row_stride + pw3), 0x00020000);
             // four 2 KB rounds in flight per trip (the loads of a round no longer wait for the
             // previous round's stores: the downsampled levels' 7-14 KB patches were latency-bound)
-            for (int i0 = 8 * tid + (pf_done ? 256 * 8 : 0); i0 < nbytes; i0 += 4 * 256 * 8) {
+            for (int i0 = 8 * tid + (pf_done ? PF_BYTES : 0); i0 < nbytes; i0 += 4 * 256 * 8) {
                 uint2 pv[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++)
@@ -892,7 +945,45 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
         const bool exact_fill = X || (!PR && split3 && P.lh >= H && P.lw >= W);
         const bool sep = staged && !(o.dbg & 1) && hs_off + nrows * PL_W * (exact_fill ? 8 : 6) <= LP::PATCH &&
                          W < 128 * P.lw;
-        if (sep && exact_fill) {
+        if (px && staged && !(o.dbg & 1)) {
+            // one-pass exact fill: the patch holds fp16 pixels [2R - 255, 2G - 255, 2B - 255, 0], a
+            // level pixel is the sum of the <= 2 x 2 patch pixels of its bin times 2^-(8..10), all
+            // in packed fp16.  Exact, so bit-identical to the two-pass fill below: every partial
+            // sum is an integer of magnitude <= 4 * 255 = 1,020 < 2,048 (an exact fp16 integer), a
+            // masked-off pixel adds +-0 to a nonzero (odd) term, a zero sum is +0 either way, and
+            // the power-of-two scale only changes the exponent (1 * 2^-10 is a normal fp16), which
+            // is what (_Float16)((float)s * sc) rounds to.
+            const f16px* pp = (const f16px*)patch;
+            f16px* lvl = (f16px*)sA;
+            const f16px zero4 = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+            int tl = tid;  // (the two-pass fill's thread map: column fq of every 6th row from fr0)
+            asm volatile("" : "+v"(tl));
+            const int fq = tl % PL_W, fr0 = tl < 6 * PL_W ? tl / PL_W : PL_H;
+            const ushort2 xbq = xbin[fq];
+            const int nq = xbq.y - xbq.x, mq = nq > 1 ? 1 : 0;
+            const int pwid = fx1 - fx0;
+            pp += nq ? xbq.x - fx0 : 0;
+            // (the pixel after the level plane, as below; the zero is laundered so that it is made
+            //  here: hoisted out of the tile loop it holds, or spills, a register pair of its own)
+            if (tid == 0) {
+                uint32_t z = 0u;
+                asm volatile("" : "+v"(z));
+                *(uint2*)(lvl + PL_H * PL_W) = make_uint2(z, z);
+            }
+            const _Float16 mqh = (_Float16)(float)mq, scw = nq > 1 ? (_Float16)0.001953125f : (_Float16)0.00390625f;
+            const f16px MQ = {mqh, mqh, mqh, mqh};
+            for (int r = fr0 + lr0; r < PL_H; r += 6) {
+                const ushort2 yb = ybin[r];
+                const int kh = yb.y - yb.x, m = kh > 1 ? 1 : 0;
+                const f16px* p = pp + (kh ? yb.x - fy0 : 0) * pwid;
+                const f16px p00 = p[0], p01 = p[mq], p10 = p[m * pwid], p11 = p[m * pwid + mq];
+                const _Float16 mh = (_Float16)(float)m, sc = kh > 1 ? scw * (_Float16)0.5f : scw;
+                const f16px M = {mh, mh, mh, mh}, SC = {sc, sc, sc, sc};
+                const f16px s = __builtin_elementwise_fma(__builtin_elementwise_fma(p11, MQ, p10), M,
+                                                          __builtin_elementwise_fma(p01, MQ, p00)) * SC;
+                lvl[r * PL_W + fq] = kh > 0 && nq > 0 ? s : zero4;
+            }
+        } else if (!X && sep && exact_fill) {
             // bins of n in {0, 1, 2} pixels: branch-free sums, 8-byte row-sum entries, one store
             // per level pixel (plane 0 only; the value is its own fp16 split: x1 = 0)
             typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -1633,8 +1724,13 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
         //      flight during conv3 (which reads its weights from LDS: no later global load waits
         //      on them), and stored to the patch buffer after it -- the next tile's staging
         //      latency hides behind this tile's matrix work
+        //      (X: whole pixels, PX_PER per thread = nine byte loads for the first 768 pixels --
+        //      every patch of the levels of scale >= 1.7 (<= 27 x 27), 86 % of the exact tiles at
+        //      min_face_size 5 -- kept packed, 4 bytes a pixel, and converted to fp16 pixels when
+        //      they are stored)
         uint2 pfv = make_uint2(0u, 0u);  // the prefetched bytes 8 tid .. +7, packed
-        int pf_n = 0;
+        uint32_t pfx[PX_PER] = {};       // (X) the prefetched pixels PX_PER tid .. +PX_PER - 1, packed
+        int pf_n = 0;                    // prefetched bytes (X: pixels), 0 = none
         {
             constexpr int FPW = PT_H * PT_W / 64;  // 16-cell fragments per wave
             // two passes of FPW/2 fragments each: conv3 + heads per pass keeps the accumulators
@@ -1682,9 +1778,10 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
             {
                 // the loads are issued on every tile (a dummy read of the first frame byte when
                 // there is nothing to prefetch), so both paths leave the same count of loads in
-                // flight and the waits for the head weights above stay partial
+                // flight (8 byte loads; X: 9) and the waits for the head weights above stay partial
+                // (X, from the ISA: the four head-weight loads are waited for at vmcnt(12) .. (9))
                 const uint8_t* pf_src = frames;
-                int qw3 = 1, nb2 = 1, pf_rows = 0;
+                int qw3 = 1, nb2 = 1, pf_rows = 0, qpw = 1;  // (pf_rows: the patch's rows, 0 = no prefetch)
                 const int64_t nt = __builtin_amdgcn_readfirstlane(s_next);
                 if (nt < total_tiles && !(o.dbg & 64)) {
                     int L2 = L;  // nt > blk
@@ -1700,18 +1797,31 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
                         const int gy0 = udiv_est((2 * oy2 + lr2) * H, Q.lh), gy1 = udiv_est((2 * oy2 + ry + 1) * H + Q.lh - 1, Q.lh);
                         const int gx0 = udiv_est(2 * ox2 * W, Q.lw), gx1 = udiv_est((2 * ox2 + rx + 1) * W + Q.lw - 1, Q.lw);
                         const int w3 = (gx1 - gx0) * 3, nb = (gy1 - gy0) * w3;
-                        if ((int64_t)(gy1 - gy0) * w3 <= LP::PATCH && nb > 0) {
+                        // (the fit test as the next tile's head has it)
+                        if ((X ? (int64_t)(gy1 - gy0) * (gx1 - gx0) * 8 : (int64_t)(gy1 - gy0) * w3) <= LP::PATCH && nb > 0) {
                             pf_src = frames + (int64_t)b2i * frame_stride + (int64_t)gy0 * row_stride + gx0 * 3;
                             qw3 = w3;
                             nb2 = nb;
-                            pf_rows = 1;
+                            pf_rows = gy1 - gy0;
+                            qpw = gx1 - gx0;
                         }
                     }
                 }
-                const int ext = pf_rows ? (nb2 / qw3 - 1) * (int)row_stride + qw3 : 1;
-                pfv = patch_bytes8(__builtin_amdgcn_make_buffer_rsrc((void*)pf_src, 0, ext, 0x00020000), 8 * tid, qw3,
-                                   (int)row_stride);
-                pf_n = pf_rows ? nb2 : 0;
+                // (the descriptor's words made scalar explicitly: they are wave-uniform, but where the
+                //  compiler cannot prove it, it wraps every load below in a waterfall loop -- seen on
+                //  the PR variant, +1.5k cycles per tile)
+                const int ext = __builtin_amdgcn_readfirstlane(pf_rows ? (pf_rows - 1) * (int)row_stride + qw3 : 1);
+                const uint64_t pfa = (uint64_t)pf_src;
+                const uint64_t pfu = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pfa) |
+                                     (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pfa >> 32)) << 32;
+                const __amdgpu_buffer_rsrc_t rpf = __builtin_amdgcn_make_buffer_rsrc((void*)pfu, 0, ext, 0x00020000);
+                if (X) {
+                    patch_px3(rpf, PX_PER * tid, qpw, max(pf_rows, 1), (int)row_stride, pfx);
+                    pf_n = pf_rows * qpw;
+                } else {
+                    pfv = patch_bytes8(rpf, 8 * tid, qw3, (int)row_stride);
+                    pf_n = pf_rows ? nb2 : 0;
+                }
             }
             // head biases of the lane's accumulator rows 4 lkx + i (group 0: conv4_1 0, 1, conv4_2
             // 0, 1; group 1: conv4_2 2, 3; groups 2, 3 hold no heads)
@@ -2016,7 +2126,17 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
             }
         }
         if (X || (PR && pf_n > 0)) __syncthreads();  // conv3's weights (under the patch bytes) are no longer read
-        if (pf_n > 0 && 8 * tid < pf_n) *(uint2*)((uint8_t*)sP + 8 * tid) = pfv;
+        if (X) {
+            // the prefetched pixels as the next tile's fp16 patch pixels (pixels past the patch
+            // read 0 and land past its end, inside the buffer: PX_ROUND * 8 <= PATCH)
+            static_assert(PX_ROUND * 8 <= LP::PATCH, "the prefetch round fits the patch buffer");
+            if (pf_n > 0) {
+#pragma unroll
+                for (int j = 0; j < PX_PER; j++) ((f16px*)sP)[PX_PER * tid + j] = px_f16(pfx[j]);
+            }
+        } else if (pf_n > 0 && 8 * tid < pf_n) {
+            *(uint2*)((uint8_t*)sP + 8 * tid) = pfv;
+        }
         pf_done = pf_n > 0;
         if (tid == 0) {  // every thread read s_tile / s_cend before this tile's barriers
             s_tile = (int)next_tile;
@@ -2029,7 +2149,7 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
 }
 
 // tiles of the leading levels the exact-levels variant can take: upsampled (lh >= H, lw >= W,
-// no precomputed level) and every tile's frame patch + 8-byte row sums within its staging buffer
+// no precomputed level) and every tile's frame patch as fp16 pixels within its staging buffer
 // (bounds: a tile's 42-pixel level span covers at most 42 H / lh + 2 frame rows / columns)
 int64_t pnet_pre_from(const std::vector<PNetLevel>& lv, int64_t total_tiles) {
     int64_t from = total_tiles;
@@ -2043,12 +2163,14 @@ int64_t pnet_pre_from(const std::vector<PNetLevel>& lv, int64_t total_tiles) {
 int64_t pnet_exact_tiles(const std::vector<PNetLevel>& lv, int H, int W, int64_t total_tiles) {
     for (const auto& L : lv) {
         const int rows = (PL_H * H + L.lh - 1) / L.lh + 2, cols = (PL_W * W + L.lw - 1) / L.lw + 2;
-        const int hs_off = (rows * cols * 3 + 7) & ~7;
-        const bool fits = rows * cols * 3 <= PnLds<true>::PATCH && hs_off + rows * PL_W * 8 <= PnLds<true>::PATCH;
-        if (L.lh < H || L.lw < W || L.pre || !fits || W >= 128 * L.lw) return L.tile_beg;
+        // (the patch as fp16 pixels for the one-pass fill: rows, cols <= PL + 2 on an upsampled
+        //  level, so it always fits -- the static_assert below)
+        const bool fits = rows * cols * 8 <= PnLds<true>::PATCH;
+        if (L.lh < H || L.lw < W || L.pre || !fits) return L.tile_beg;
     }
     return total_tiles;
 }
+static_assert((PL_H + 2) * (PL_W + 2) * 8 <= PnLds<true>::PATCH, "an exact level's largest frame patch as fp16 pixels");
 
 static_assert(PNET_VR_SLOT == VR_SLOT, "mtcnn.hpp's VR slot size");
 
@@ -2078,7 +2200,8 @@ static int pnet_wgs(const char* name, int mx) {
     return v >= 1 && v <= mx ? v : mx;
 }
 
-// grid of the exact-levels launch over `exact_tiles` tiles (the vertical-reuse slots it needs)
+// grid of the exact-levels or the PR launch over that many tiles (the vertical-reuse slots it
+// needs): both are sized here, so the slots the caller allocates cover the grid that is launched
 int64_t pnet_x_grid(int64_t exact_tiles) {
     if (exact_tiles <= 0) return 0;
     int chunk = 0, quota = 0;
@@ -2148,9 +2271,7 @@ void launch_pnet(bool dense, const uint8_t* frames, int64_t frame_stride, int64_
                                                                   pre_from, d_tile_ctr + 1, w, og, exact_tiles, quota, chunk);
     }
     if (pre_from < total_tiles) {  // PR variant: tiles [pre_from, total_tiles)
-        const int64_t rest = total_tiles - pre_from;
-        int64_t grid = std::min<int64_t>(rest, (int64_t)cus * PnLds<true>::GPC);
-        if (quota > 0) grid = std::max<int64_t>(grid, (rest + (int64_t)quota * chunk - 1) / ((int64_t)quota * chunk));
+        const int64_t grid = pnet_x_grid(total_tiles - pre_from);
         const char* ve = std::getenv("VTF_PNET_VR");
         if (o.vr && grid <= o.vr_slots && ve && std::atoi(ve) != 0)
             k_pnet<false, false, true, true><<<(unsigned)grid, 256, 0, st>>>(

@@ -117,6 +117,8 @@ struct Mtcnn {
     // parity introspection (vtf_mtcnn_stage1_keys): the last call's stage-1 candidate keys
     bool keep_s1 = false;
     std::vector<uint64_t> s1_keys;
+    // (vtf_mtcnn_pnet_plan) the last call's PNet plan: per level 1 = the exact-levels kernel's, 0 = not
+    std::vector<int32_t> pnet_plan;
     // kernel timing (vtf_mtcnn_profile)
     bool prof = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -937,6 +939,8 @@ static void detect(Mtcnn& m, const uint8_t* frames, int on_dev, int B, int H, in
     if (po.dbg & 256) po.clk = m.ar.get<unsigned long long>(S_CLK, 16);
     if (po.clk) VTF_HIP(hipMemsetAsync(po.clk, 0, 128, st));
     const int64_t x_tiles = pnet_exact_tiles(lv, H, W, tiles);
+    m.pnet_plan.assign(NL, 0);
+    for (int i = 0; i < NL; i++) m.pnet_plan[i] = lv[i].tile_beg < x_tiles ? 1 : 0;
     // one vertical-reuse slot per workgroup of the exact-levels or the PR launch (the same grid
     // rule; the two run one after the other on the stream and share the slots)
     // (allocated only when the opt-in variant is on: VTF_PNET_VR=1, read per det-batch as
@@ -1165,6 +1169,15 @@ int vtf_mtcnn_stage1_keys(vtf_mtcnn_t h, int enable, uint64_t* out, int64_t cap,
         if (enable >= 0) m.keep_s1 = enable != 0;
         *out_n = (int64_t)m.s1_keys.size();
         std::memcpy(out, m.s1_keys.data(), (size_t)std::min<int64_t>(cap, *out_n) * 8);
+    });
+}
+
+int vtf_mtcnn_pnet_plan(vtf_mtcnn_t h, int32_t* out, int64_t cap, int64_t* out_n) {
+    return guarded_on(h ? h->m.device : -1, [&] {
+        VTF_CHECK(h && out_n && cap >= 0 && (out || cap == 0), VTF_E_ARG, "bad argument");
+        const Mtcnn& m = h->m;
+        *out_n = (int64_t)m.pnet_plan.size();
+        std::memcpy(out, m.pnet_plan.data(), (size_t)std::min<int64_t>(cap, *out_n) * 4);
     });
 }
 

@@ -99,6 +99,14 @@ class MTCNN:
         nat.check(nat.lib().vtf_mtcnn_stage1_keys(self._h, -1, out.ctypes.data, n.value, ctypes.byref(n)))
         return out[:n.value]
 
+    def pnet_plan(self):
+        """Parity introspection: per pyramid level of the last call, 1 if the exact-levels kernel
+        (one-pass level fill) is planned to take it, else 0."""
+        out = np.empty(64, np.int32)
+        n = ctypes.c_int64(0)
+        nat.check(nat.lib().vtf_mtcnn_pnet_plan(self._h, out.ctypes.data, out.size, ctypes.byref(n)))
+        return out[:min(n.value, out.size)].copy()
+
     def profile(self, enable):
         """Start (enable=True, resets) or stop kernel timing of the fused pyramid+PNet kernel;
         returns (ms, launches, algorithmic flops, frames) accumulated so far."""
