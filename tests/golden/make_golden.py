@@ -1061,8 +1061,97 @@ def gen_classify():
     print('classify', {k: v.shape for k, v in out.items()})
 
 
+def _savez_stable(path, arrays):
+    """An .npz whose bytes depend on the arrays alone (np.savez stamps every member with the
+    time of writing): fixed member dates, names in sorted order."""
+    import zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            zi = zipfile.ZipInfo(name + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(zi, 'w') as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[name]), allow_pickle=False)
+
+
+def gen_kmeans_edges():
+    """sklearn 1.7.2's answers at the edges of the K-means / score kernels' envelope, on the
+    inputs of tests/kmeans_inputs.py (stored as hashes), one OpenMP thread as _sk_kmeans_sweep:
+    end-to-end labels and scores for k > 16, D = 768, D % 16 != 0 and D < 32; labels on
+    duplicated rows, where clusters go empty, with how often the stand-in (which equals sklearn
+    there) relocates; sklearn's own E-step labels on near-tied rows; _euclidean_dense_dense; and
+    silhouette samples / CH / DB for label sets of 2, 16 and 40 clusters and one with a
+    singleton."""
+    import sklearn.metrics
+    from sklearn.cluster import _kmeans
+    from sklearn.cluster._k_means_common import _euclidean_dense_dense_wrapper
+    from threadpoolctl import threadpool_limits
+    sys.path.insert(0, os.path.dirname(HERE))
+    sys.path.insert(0, ROOT)
+    import kmeans_inputs as ki
+    from oracle.kmeans import CpuGrouper
+
+    def scores(X, lb):
+        return (sklearn.metrics.silhouette_score(X, lb), sklearn.metrics.calinski_harabasz_score(X, lb),
+                sklearn.metrics.davies_bouldin_score(X, lb))
+
+    class Counting(CpuGrouper):
+        def __init__(self):
+            self.relocations = self.empty_averages = 0
+
+        def _relocate_empty(self, *a):
+            self.relocations += 1
+            return super()._relocate_empty(*a)
+
+        def _average(self, sums, w, old):
+            self.empty_averages += int(np.any(w == 0))
+            return super()._average(sums, w, old)
+
+    out = {}
+    for N, D, k in ki.EDGE_CASES:
+        X = ki.edge_case(N, D, k)
+        lb = _sk_kmeans_sweep(X, [k], 1)[0]
+        key = 'edge_%d_%d_%d' % (N, D, k)
+        out[key + '_sha'] = np.array(ki.sha(X))
+        out[key + '_labels'] = lb.astype(np.int8)
+        out[key + '_scores'] = np.array(scores(X, lb), np.float64)
+    for seed in ki.DUP_SEEDS:
+        X = ki.dup_case(seed)
+        lb = _sk_kmeans_sweep(X, [ki.DUP_K], 1)[0]
+        cg = Counting()
+        assert np.array_equal(cg.kmeans(X, ki.DUP_K), lb), 'the stand-in differs from sklearn: counts mean nothing'
+        key = 'dup_%d' % seed
+        out[key + '_sha'] = np.array(ki.sha(X))
+        out[key + '_labels'] = lb.astype(np.int8)
+        out[key + '_relocations'] = np.int64(cg.relocations)
+        out[key + '_empty_averages'] = np.int64(cg.empty_averages)
+    for N, D, k in ki.TIES_CASES:
+        X, C = ki.ties_case(N, D, k)
+        with threadpool_limits(limits=1, user_api='openmp'):
+            lb, _ = _kmeans._labels_inertia_threadpool_limit(X, np.ones(N, np.float32), C, n_threads=1)
+        key = 'ties_%d_%d_%d' % (N, D, k)
+        out[key + '_sha'] = np.array(ki.sha(X, C))
+        out[key + '_labels'] = lb.astype(np.int8)
+    for D in ki.SHIFT_D:
+        a, b = ki.shift_case(D)
+        out['shift_%d_sha' % D] = np.array(ki.sha(a, b))
+        out['shift_%d' % D] = np.array([_euclidean_dense_dense_wrapper(x, y, False) for x, y in zip(a, b)],
+                                       np.float32)
+    for N, D in ki.SCORE_CASES:
+        X, sets = ki.score_case(N, D)
+        key = 'score_%d_%d' % (N, D)
+        out[key + '_sha'] = np.array(ki.sha(X, *[sets[n] for n in sorted(sets)]))
+        for name, lb in sets.items():
+            out['%s_%s_sil' % (key, name)] = sklearn.metrics.silhouette_samples(X, lb).astype(np.float32)
+            out['%s_%s_chdb' % (key, name)] = np.array(scores(X, lb)[1:], np.float64)
+    _savez_stable(os.path.join(HERE, 'kmeans_edges.npz'), out)
+    print('kmeans_edges: %d arrays, %d bytes; relocations %s, empty averages %s' % (
+        len(out), os.path.getsize(os.path.join(HERE, 'kmeans_edges.npz')),
+        [int(out['dup_%d_relocations' % s]) for s in ki.DUP_SEEDS],
+        [int(out['dup_%d_empty_averages' % s]) for s in ki.DUP_SEEDS]))
+
+
 if __name__ == '__main__':
     which = sys.argv[1:] or ['mtcnn', 'facenet', 'vit', 'grouping', 'yolo', 'kmeans', 'rcnn', 'dupes', 'boxes', 'shapes', 'chain',
-                             'scale', 'c3', 'iom', 'b1', 'classify', 'meta']
-    for w in which:
-        globals()['gen_' + w]()
+                             'scale', 'c3', 'iom', 'b1', 'classify', 'kmeans_edges', 'meta']
+    for w in which:  # 'kmeans_edges' or 'gen_kmeans_edges'
+        globals()['gen_' + w.removeprefix('gen_')]()

@@ -121,7 +121,11 @@ __global__ __launch_bounds__(256) void k_sqdist_rows(const float* __restrict__ X
 //   sgemm, blocked kernel otherwise: D in K blocks (448, or the two halves of a remainder
 //           between 448 and 896 rounded up to 16), sequential fma per block from 0, and
 //           pd = pd - 2 acc after every block.
-// (Exact for D % 16 == 0; other D follow the same rules without that verification.)
+// The same rules hold off those shapes: the numpy restatement of them (oracle/kmeans.py
+// estep_distances) equals sklearn's own label pass on near-tied rows for D = 31, 32, 40, 100,
+// 520, 776, 1000 and 1029 (D < 32 and D % 16 != 0 included) and k up to 64
+// (tests/test_kmeans_oracle.py), and k_estep equals the restatement bit for bit on the same rows
+// (tests/test_kmeans_kernels_gpu.py).
 // (np_einsum_sq and the K blocking live in sk_order.hpp.)
 
 __global__ void k_csq(const float* __restrict__ C, int k, int D, float* __restrict__ csq) {

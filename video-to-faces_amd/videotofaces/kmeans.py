@@ -63,7 +63,13 @@ class Grouper:
         N, D = Xc.shape
         self._bind()
         out = torch.empty((ids.size, N), dtype=torch.float32, device=self.device)
-        nat.check(nat.lib().vtf_sqdist_rows(self._h, nat.ptr(Xc), N, D, ids.ctypes.data, ids.size, nat.ptr(out)))
+        # vtf_sqdist_rows stages its T rows in 64 KiB of LDS (and takes T <= 16): wide rows go in
+        # several calls.  Every output row depends on its own id alone, so the bits are the same.
+        step = max(1, min(16, (64 * 1024) // (4 * D)))
+        for s in range(0, ids.size, step):
+            part = ids[s:s + step]
+            nat.check(nat.lib().vtf_sqdist_rows(self._h, nat.ptr(Xc), N, D, part.ctypes.data, part.size,
+                                                nat.ptr(out[s:s + step])))
         return out.cpu().numpy()
 
     def _kmeans_plusplus(self, Xc, n_clusters, sample_weight, random_state):
