@@ -22,7 +22,7 @@ struct PNetW {
     // fp16 matrix-core path (copied to LDS per tile); null -> fp32 MFMA path (see k_pnet)
     const uint16_t* c3h;
     const uint16_t* c2h;  // conv2: [2][16][96], the 90 (tap, ci) products packed in 3 k-steps (mtcnn_runtime)
-    const uint16_t* c1h;  // conv1: [2][16][64], k = ky * 16 + kx * 4 + c (c = 3, kx = 3, ky = 3, co >= 10 zero)
+    const uint16_t* c1h;  // conv1: [2][16][64], k = ky * 16 + kx * 4 + c (c = 3, kx = 3, ky = 3 zero; rows co >= 10 repeat rows 8, 9)
     // both 1x1 heads as fp16 split planes [2][32 rows][32 k] (rows 0,1 conv4_1, 2..5 conv4_2, the
     // rest zero); k = 16 s + 8 hk + i holds channel 16 s + 8 (i >> 2) + (i & 3) + 4 hk: exactly
     // the conv3 accumulator registers 8 s + i of lane half hk (k_pnet's 32x32x16 conv3), so the

@@ -471,10 +471,26 @@ constexpr int PP_H = PT_H + 4, PP_W = PT_W + 4;       // pooled 20 x 20
 constexpr int PC_H = PT_H + 2, PC_W = PT_W + 2;       // conv2 out 18 x 18
 constexpr int P_LVL = 3 * PL_H * PL_W;                // 5292
 constexpr int P_C2 = 16 * PC_H * PC_W;                // 5184
-// pooled conv1: fp32 [10][cells], or fp16 split planes [2][cells][12] (ch 10, 11 zero; conv2 reads
-// 8 halves from channel 8 into the next cell, against zero weights) + 4 halves of end padding
-constexpr int PQ_C = 12;
-constexpr int P_POOL0 = (10 * PP_H * PP_W > PQ_C * PP_H * PP_W) ? 10 * PP_H * PP_W : PQ_C * PP_H * PP_W;
+// pooled conv1: fp32 [10][cells], or fp16 split planes, each [pad | C | A] (offsets in halves):
+//   A[cell][ch 0..7]                                    16 B per cell
+//   C[cell] = [c8 c9 of the cell | c8 c9 of cell + 1]    8 B per cell
+// so every conv2 operand is one 16-byte read: channels 0..7 of a tap from A (16-byte aligned:
+// ds_read_b128), and the 16 bytes at C[(r, c)] = channels 8, 9 of columns c, c + 1, c + 1, c + 2 --
+// a tap row's three taps plus one slot that meets zero weights.  Row pitch PP_W cells in both
+// (scripts/lds_bank_model.py: 386 LDS cycles per tile and plane with conv2's row-aligned
+// fragments, 587 for the [cell][12] map with its dword gathers that this replaces).  The second
+// pair of a cell is written by conv1's lanes 10, 11, which compute channels 8, 9 again (weight
+// rows 10.. repeat rows 8, 9: mtcnn_runtime) and store into the PREVIOUS cell.  For a row's first
+// cell that is the last cell of the row above, whose second pair is never read (reads end at
+// cell 18 of a row); for cell 0 it is the 16-byte pad in front of C, never read either.
+constexpr int PQ_NPP = PP_H * PP_W;
+constexpr int PQ_PAD = 8;                          // halves in front of C (cell -1's second pair)
+constexpr int PQ_OC = PQ_PAD;                      // C of a plane
+constexpr int PQ_OA = PQ_OC + 4 * PQ_NPP;          // A of a plane
+constexpr int PQ_PL = PQ_OA + 8 * PQ_NPP;          // halves per plane: 4808 (9,616 B)
+constexpr int PQ_ROW_A = PP_W * 8, PQ_ROW_C = PP_W * 4;  // halves per pooled row
+static_assert(PQ_OA % 8 == 0 && PQ_PL % 8 == 0 && PQ_OC % 4 == 0, "A is read 16 bytes aligned, C 8 bytes");
+constexpr int P_POOL0 = 10 * PQ_NPP > PQ_PL ? 10 * PQ_NPP : PQ_PL;
 // during conv3 the pooled buffer holds the next tile's first 2 KB of frame patch (floats 0..511)
 // and conv3's split weights [2][32][144] halves (floats 512..5119, rows of 72 dwords: conflict-free
 // for the 16-byte A-operand reads), so conv3 issues no global loads
@@ -643,7 +659,7 @@ static_assert(PNET_GROUPS_PER_CU >= 2, "k_pnet tile too large for 2 workgroups p
 template <bool X>
 struct PnLds {
     static constexpr int A = X ? P_C2 + 4 : P_A;                     // floats
-    static constexpr int POOL = X ? PQ_C * PP_H * PP_W : P_POOL;      // floats (split pooled conv1)
+    static constexpr int POOL = X ? PQ_PL : P_POOL;                   // floats (split pooled conv1: 2 planes of PQ_PL halves)
     static constexpr int W3 = X ? 0 : P_W3;                           // conv3 weights (floats)
     static constexpr int PATCH = (POOL - 4) * 4;                      // staged frame patch (bytes)
     static constexpr int BYTES = (A + POOL) * 4 + (PL_H + PL_W) * 4 + 16 + 64 + 256;  // + s_c3
@@ -661,11 +677,13 @@ struct PnLds {
 // fragments).  The kept rows go through a per-workgroup slot in global memory (written after
 // the tile's conv1 / conv2 with 16-byte stores, read back by LDS-DMA into rows 0..3 / 0, 1 after
 // the next tile's fill / conv1), so the LDS plan is unchanged (four workgroups per CU).
-constexpr int VR_POOL_BYTES = 2 * 4 * PP_W * PQ_C * 2;  // pooled rows 16..19 of both planes: 3840 B
+constexpr int VR_POOL_A = 4 * PQ_ROW_A * 2, VR_POOL_C = 4 * PQ_ROW_C * 2;  // 4 pooled rows of a plane's A / C: 1280 + 640 B
+constexpr int VR_POOL_BYTES = 2 * (VR_POOL_A + VR_POOL_C);  // pooled rows 16..19 of both planes, [A | C] each: 3840 B
 constexpr int VR_C2_BYTES = 2 * 2 * PC_W * 16 * 2;      // conv2 rows 16, 17 of both planes: 2304 B
 constexpr int VR_SLOT = VR_POOL_BYTES + VR_C2_BYTES;
 constexpr int VR_LROW = 8;                              // first level row a continuing tile fills
-static_assert(VR_POOL_BYTES == 3840 && VR_C2_BYTES == 2304, "VR slot pieces (the DMA piece split below)");
+static_assert(VR_POOL_BYTES == 3840 && VR_C2_BYTES == 2304 && VR_POOL_A == 1024 + 16 * 16 && VR_POOL_C == 40 * 16,
+              "VR slot pieces (the DMA piece split below)");
 
 struct TileGeo {
     int b, ty, tx;
@@ -1105,16 +1123,21 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
         if (VR && cont) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         mark(3);  // 3: level tile fill
-        // (VR) pooled rows 0..3 <- the previous tile's rows 16..19 from the workgroup's slot: plane p
-        // rows 0..3 are bytes [p 9600, p 9600 + 1920) of sP; one 1 KB LDS-DMA piece per wave (the
-        // patch and row sums that used sP are dead), waited for before conv1's closing barrier
+        // (VR) pooled rows 0..3 <- the previous tile's rows 16..19 from the workgroup's slot: rows
+        // 0..3 of a plane are the first 1280 B of its A and the first 640 B of its C; per plane one
+        // wave takes A's first 1 KB, the other A's last 256 B and C (LDS-DMA pieces; the patch and
+        // row sums that used sP are dead), waited for before conv1's closing barrier
         uint8_t* vslot = VR ? o.vr + (int64_t)blockIdx.x * VR_SLOT : nullptr;
         if (VR && cont) {
             const int w = __builtin_amdgcn_readfirstlane(wave), pl = w >> 1, hf = w & 1;
-            if (!hf || lane < (VR_POOL_BYTES / 2 - 1024) / 16)
-                __builtin_amdgcn_global_load_lds(
-                    (const void __attribute__((address_space(1)))*)(vslot + pl * (VR_POOL_BYTES / 2) + hf * 1024 + lane * 16),
-                    (void __attribute__((address_space(3)))*)((uint8_t*)sP + pl * (PP_H * PP_W * PQ_C * 2) + hf * 1024), 16, 0, 0);
+            const uint8_t* src = vslot + pl * (VR_POOL_BYTES / 2);
+            uint8_t* dst = (uint8_t*)sP + pl * (PQ_PL * 2);
+            if (!hf || lane < (VR_POOL_A - 1024) / 16)
+                __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + hf * 1024 + lane * 16),
+                                                 (void __attribute__((address_space(3)))*)(dst + PQ_OA * 2 + hf * 1024), 16, 0, 0);
+            if (hf && lane < VR_POOL_C / 16)
+                __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + VR_POOL_A + lane * 16),
+                                                 (void __attribute__((address_space(3)))*)(dst + PQ_OC * 2), 16, 0, 0);
         }
 
         // ---- 2. conv1 (3->10, 3x3) + PReLU + maxpool 2x2 ceil.  Default: fp16 matrix cores on
@@ -1136,7 +1159,6 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
             // other half's partials of the same channel: afterwards every lane holds main and cross
             // of 2 cells (q = 0, 1 in the main lanes, q = 2, 3 in the cross lanes) and combines them
             // 2048-scaled with one fma each (split_u) -- no padding rows, no duplicated lanes.
-            constexpr int NPP = PP_H * PP_W;
             constexpr int FB = PP_W / 4;              // 4-cell column blocks per row pair
             constexpr int NF1 = (PP_H / 2) * FB;      // fragments per tile
             static_assert(PP_W % 4 == 0 && PP_H % 2 == 0, "conv1 fragments are 2 x 4 pooled cells");
@@ -1156,7 +1178,9 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
             for (int s = 0; s < 3; s++)
                 wb[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rw1h, woff, 32 * s, 0));
             // bias 2048-scaled (exact): the epilogue works on u = 2048 v (split_u)
-            const float b1s = lrx < 10 ? wf[PW_C1B + lrx] * 2048.f : 0.f, a1 = lrx < 10 ? wf[PW_P1 + lrx] : 0.f;
+            // (lanes 10..15 compute channels 8, 9 again: weight rows 10.. repeat rows 8, 9)
+            const int ch1 = lrx < 10 ? lrx : 8 + (lrx & 1);
+            const float b1s = wf[PW_C1B + ch1] * 2048.f, a1 = wf[PW_P1 + ch1];
             // the tile's conv1 window lies inside the level: no per-corner bounds checks
             const bool interior = 2 * (oy0 + PP_H - 1) + 1 < L1h && 2 * (ox0 + PP_W - 1) + 1 < L1w;
             // pool-then-activate is exact when every channel's slope is >= 0 (PReLU and rounding
@@ -1175,9 +1199,12 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
             const int lpix = (2 * (cq >> 2) + (corner >> 1)) * PL_W + 2 * (cq & 3) + (corner & 1) + 2 * hk;
             // the cells this lane ends with: 2 q + 4 ((lane >> 4) & 1) + (lane >> 5), q = 0, 1
             const int cbase = 4 * ((ln >> 4) & 1) + (ln >> 5);
-            // pooled-map slot of the lane's channel (lanes 12..15 repeat channels 10, 11, which
-            // conv2 never reads)
-            const int qch = lrx < 12 ? lrx : 10 + (lrx & 1);
+            // pooled-map slot of the lane's channel: cell << qsh halves from qoff.  Channels 0..7 go
+            // to A, 8 and 9 to the cell's first pair in C, and lanes 10, 11 store channels 8, 9 once
+            // more as the second pair of the previous cell (PQ_*; lanes 12..15 repeat lanes 10, 11:
+            // same value, same address)
+            const int qsh = lrx < 8 ? 3 : 2;
+            const int qoff = lrx < 8 ? PQ_OA + lrx : PQ_OC + (lrx < 10 ? lrx - 8 : (lrx & 1) - 2);
             // residual-level cross operand [0 | w0] (general variant only)
             f16x8 wx[3] = {};
             if (!exact) {
@@ -1264,9 +1291,9 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
                             }
                             _Float16 x0, x1;
                             split_u(out, x0, x1);
-                            _Float16* qp = sQ + (py * PP_W + px) * PQ_C + qch;
+                            _Float16* qp = sQ + ((py * PP_W + px) << qsh) + qoff;
                             qp[0] = x0;
-                            qp[NPP * PQ_C] = x1;
+                            qp[PQ_PL] = x1;
                         }
                     }
                 }
@@ -1397,10 +1424,10 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
                             }
                             _Float16 x0, x1;
                             split_u(out, x0, x1);
-                            if (r16 < PQ_C) {
-                                _Float16* qp = sQ + (py[u] * PP_W + px) * PQ_C + r16;
+                            if (r16 < 12) {
+                                _Float16* qp = sQ + ((py[u] * PP_W + px) << qsh) + qoff;
                                 qp[0] = x0;
-                                qp[NPP * PQ_C] = x1;
+                                qp[PQ_PL] = x1;
                             }
                         }
                     }
@@ -1496,8 +1523,11 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
         const bool vr_next = VR && __builtin_amdgcn_readfirstlane(s_next) == blk + 1 && tg.ty + 1 < P.tiles_y;
         if (VR && vr_next && tid < VR_POOL_BYTES / 16) {
             // pooled rows 16..19 of both planes -> the slot (read again after the next tile's fill)
+            // (per plane [A rows | C rows], as the read-back above takes them)
             const int pl = tid / (VR_POOL_BYTES / 32), q = tid - pl * (VR_POOL_BYTES / 32);
-            const uint4 v = *(const uint4*)((const uint8_t*)sP + pl * (PP_H * PP_W * PQ_C * 2) + 16 * PP_W * PQ_C * 2 + q * 16);
+            const int so = q < VR_POOL_A / 16 ? (PQ_OA + 16 * PQ_ROW_A) * 2 + q * 16
+                                              : (PQ_OC + 16 * PQ_ROW_C) * 2 + (q - VR_POOL_A / 16) * 16;
+            const uint4 v = *(const uint4*)((const uint8_t*)sP + pl * (PQ_PL * 2) + so);
             *(uint4*)(vslot + tid * 16) = v;
         }
         if (VR && cont) {
@@ -1518,15 +1548,18 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
             if (split3 && !(o.dbg & 4)) {
                 // fp16 matrix cores on split operands (as conv3), computed TRANSPOSED (rows = the 16
                 // output channels, A = weights; columns = 16 conv2 positions, B = the pooled map), K =
-                // 90 packed into 3 steps of 32: step 0 / 1 = channels 0-7 of taps g / 4 + g for lane
-                // group g (one 16-byte read per plane); step 2 = 4 dwords per lane: group 0 channels
-                // 0-7 of tap 8, groups 1 / 2 channels 8, 9 of taps 0-3 / 4-7, group 3 channels 8, 9
-                // of tap 8 (+ 3 zero-weight slots).  Each lane ends with 4 consecutive output channels
-                // of one position: one 8-byte store per plane.  Main and 2^11-scaled cross products
-                // in separate accumulators.
-                constexpr int NPP = PP_H * PP_W;
+                // 90 packed into 3 steps of 32, every operand one 16-byte read per plane: step 0 / 1 =
+                // channels 0-7 of taps g / 4 + g for lane group g, from sub-plane A (ds_read_b128);
+                // step 2 = group 0 channels 0-7 of tap 8 from A, group g = 1..3 the 16 bytes at
+                // C[(r + g - 1, c)]: channels 8, 9 of tap row g - 1's columns c, c + 1, c + 1, c + 2
+                // (the third pair meets zero weights; PQ_* above).  Fragments are row-aligned --
+                // which 16 positions a fragment takes is free, and this map is what keeps the
+                // reads off each other's banks (scripts/lds_bank_model.py): fragment f < nrow is
+                // columns 0..15 of row row0 + f, the rest take columns 16, 17 in strips of 8 rows.
+                // Each lane ends with 4 consecutive output channels of one position: one 8-byte
+                // store per plane.  Main and 2^11-scaled cross products in separate accumulators.
                 const _Float16* sH = (const _Float16*)sP;
-                typedef const volatile __attribute__((address_space(3))) uint32_t lds_u32;
+                typedef const __attribute__((address_space(3))) f16x8 lds_f16x8;
                 f16x8 w0[3], w1[3];
                 const int woff = (lrx * 96 + 8 * lkx) * 2;
 #pragma unroll
@@ -1535,13 +1568,11 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
                     w1[s3] = __builtin_bit_cast(f16x8,
                                                 __builtin_amdgcn_raw_buffer_load_b128(rw2h, woff, 16 * 96 * 2 + 64 * s3, 0));
                 }
-                // operand offsets (halves) relative to the position's pooled cell
-                auto tapoff = [](int t) { return ((t / 3) * PP_W + t % 3) * PQ_C; };
+                // operand offsets (halves) relative to the position's pooled cell in A (8 halves a cell);
+                // step 2: cell << sh2 halves from o2 (group 0 in A, the others in C, 4 halves a cell)
+                auto tapoff = [](int t) { return PQ_OA + ((t / 3) * PP_W + t % 3) * 8; };
                 const int o0 = tapoff(lkx), o1 = tapoff(4 + lkx);
-                int o2[4];
-#pragma unroll
-                for (int jj = 0; jj < 4; jj++)
-                    o2[jj] = lkx == 0 ? tapoff(8) + 2 * jj : lkx == 3 ? tapoff(8) + 8 : tapoff(4 * (lkx - 1) + jj) + 8;
+                const int sh2 = lkx == 0 ? 3 : 2, o2 = lkx == 0 ? tapoff(8) : PQ_OC + (lkx - 1) * PQ_ROW_C;
                 float bb[4], aa[4];  // bias 2048-scaled (split_u)
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
@@ -1549,33 +1580,39 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
                     aa[i] = wf[PW_P2 + 4 * lkx + i];
                 }
                 _Float16* sO = (_Float16*)sA;
-                // (VR) continuing tile: rows 2..17 only (positions 36.., 18 fragments)
-                const int pb = cont ? 2 * PC_W : 0, nf = cont ? (NPOS - 2 * PC_W) / 16 : NF;
-                static_assert((NPOS - 2 * PC_W) % 16 == 0, "continuing-tile conv2 fragments");
+                // (VR) continuing tile: rows 2..17 only (16 row fragments + 2 strips)
+                static_assert(PC_W == 18 && PC_H % 2 == 0, "conv2 fragments: 16 columns of a row, then strips of 8 x 2");
+                const int row0 = cont ? 2 : 0, nrow = PC_H - row0, nf = nrow + (2 * nrow + 15) / 16;
+                static_assert(PC_H + (2 * PC_H + 15) / 16 == NF, "conv2 fragment count");
+                // position (row, column) of lane column lrx in fragment f; strip lanes past the last row
+                // repeat row 17 (their results are not stored)
+                auto fpos = [&](int f, int& r, int& c) {
+                    const int i = (f - nrow) * 16 + lrx;
+                    r = f < nrow ? row0 + f : row0 + (i >> 1);
+                    c = f < nrow ? lrx : 16 + (i & 1);
+                };
                 auto conv2_frags = [&](auto u_t) {
                 constexpr bool U2 = decltype(u_t)::value;
                 // (wave index through readfirstlane: `two` is then a scalar branch, not an exec mask)
                 for (int f0 = __builtin_amdgcn_readfirstlane(wave); f0 < nf; f0 += 8) {
                     const int f1 = f0 + 4;
                     const bool two = f1 < nf;
-                    const int p0 = min(pb + f0 * 16 + lrx, NPOS - 1), p1 = min(pb + (two ? f1 : f0) * 16 + lrx, NPOS - 1);
-                    const int ab0 = ((p0 / PC_W) * PP_W + (p0 % PC_W)) * PQ_C, ab1 = ((p1 / PC_W) * PP_W + (p1 % PC_W)) * PQ_C;
+                    int r0, c0p, r1, c1p;
+                    fpos(f0, r0, c0p);
+                    fpos(two ? f1 : f0, r1, c1p);
+                    const int cell0 = min(r0, PC_H - 1) * PP_W + c0p, cell1 = min(r1, PC_H - 1) * PP_W + c1p;
+                    const int ab0 = cell0 * 8, ab1 = cell1 * 8;
+                    const int ac0 = (cell0 << sh2) + o2, ac1 = (cell1 << sh2) + o2;
                     f16x8 x[3][2][2];  // [step][fragment][plane]
 #pragma unroll
                     for (int pl = 0; pl < 2; pl++) {
-                        const _Float16* base = sH + pl * NPP * PQ_C;
-                        x[0][0][pl] = ld_h8(base + ab0 + o0);
-                        x[0][1][pl] = ld_h8(base + ab1 + o0);
-                        x[1][0][pl] = ld_h8(base + ab0 + o1);
-                        x[1][1][pl] = ld_h8(base + ab1 + o1);
-                        uint32_t u0[4], u1[4];
-#pragma unroll
-                        for (int jj = 0; jj < 4; jj++) {
-                            u0[jj] = *(lds_u32*)(base + ab0 + o2[jj]);
-                            u1[jj] = *(lds_u32*)(base + ab1 + o2[jj]);
-                        }
-                        x[2][0][pl] = __builtin_bit_cast(f16x8, u0);
-                        x[2][1][pl] = __builtin_bit_cast(f16x8, u1);
+                        const _Float16* base = sH + pl * PQ_PL;
+                        x[0][0][pl] = *(lds_f16x8*)(base + ab0 + o0);
+                        x[0][1][pl] = *(lds_f16x8*)(base + ab1 + o0);
+                        x[1][0][pl] = *(lds_f16x8*)(base + ab0 + o1);
+                        x[1][1][pl] = *(lds_f16x8*)(base + ab1 + o1);
+                        x[2][0][pl] = ld_h8(base + ac0);
+                        x[2][1][pl] = ld_h8(base + ac1);
                     }
                     f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0, d0 = c0, d1 = c0;
                     if (two) {
@@ -1598,8 +1635,8 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
                     }
 #pragma unroll
                     for (int h = 0; h < 2; h++) {
-                        const int q = pb + (h ? f1 : f0) * 16 + lrx;
-                        if (q < NPOS && (h == 0 || two)) {
+                        const int rq = h ? r1 : r0, q = rq * PC_W + (h ? c1p : c0p);
+                        if (rq < PC_H && (h == 0 || two)) {
                             f16x4 v0, v1;
 #pragma unroll
                             for (int i = 0; i < 4; i++) {
@@ -1610,7 +1647,7 @@ __global__ __launch_bounds__(256, PnLds<X || PR>::GPC) void k_pnet(const uint8_t
                                 v1[i] = x1;
                             }
                             // (odd rows: channel halves swapped, see C2_SWZ)
-                            const int qo = q * 16 + ((4 * lkx) ^ (8 * ((q / PC_W) & 1)));
+                            const int qo = q * 16 + ((4 * lkx) ^ (8 * (rq & 1)));
                             *(f16x4*)(sO + qo) = v0;
                             *(f16x4*)(sO + NPOS * 16 + qo) = v1;
                         }

@@ -402,6 +402,11 @@ static void build_weights(Mtcnn& m, const float* params, int64_t n_params) {
                                 std::memcpy(&h[(size_t)co * 64 + k], &w0, 2);
                                 std::memcpy(&h[(size_t)(16 + co) * 64 + k], &w1, 2);
                             }
+                // rows 10..15 repeat rows 8, 9 in both planes: k_pnet's conv1 lanes 10, 11 compute
+                // channels 8, 9 a second time, for the pooled map's duplicate pair (PQ_*)
+                for (int pl = 0; pl < 2; pl++)
+                    for (int co = 10; co < 16; co++)
+                        std::memcpy(&h[(size_t)(16 * pl + co) * 64], &h[(size_t)(16 * pl + 8 + (co & 1)) * 64], 64 * 2);
                 uint16_t* d = nullptr;
                 VTF_HIP(hipMalloc((void**)&d, h.size() * 2));
                 VTF_HIP(hipMemcpy(d, h.data(), h.size() * 2, hipMemcpyHostToDevice));
@@ -410,8 +415,10 @@ static void build_weights(Mtcnn& m, const float* params, int64_t n_params) {
             }
             {
                 // conv2 [2][16][96]: k = 32 s + 8 g + j packs the 90 (tap, ci) products in 3 steps
-                // (k_pnet conv2): s < 2 -> tap 4 s + g, ci j; s = 2 -> g 0: tap 8, ci j; g 1 / 2:
-                // tap 4 (g - 1) + j / 2, ci 8 + j % 2; g 3: tap 8, ci 8 + j (j < 2), else zero
+                // (k_pnet conv2): s < 2 -> tap 4 s + g, ci j; s = 2 -> g 0: tap 8, ci j; g 1..3: tap
+                // row g - 1 against the pooled map's 16 bytes [c8 c9 (col) | c8 c9 (col + 1) | c8 c9
+                // (col + 1) | c8 c9 (col + 2)]: pairs 0, 1, 3 = taps 3 (g - 1) + 0, 1, 2 with ci 8 +
+                // j % 2, pair 2 (col + 1 a second time) zero
                 std::vector<uint16_t> h((size_t)2 * 16 * 96, 0);
                 const float* W = raw[3];  // [16][10][3][3]
                 for (int co = 0; co < 16; co++)
@@ -420,8 +427,7 @@ static void build_weights(Mtcnn& m, const float* params, int64_t n_params) {
                         int tap = -1, ci = -1;
                         if (st < 2) tap = 4 * st + g, ci = j;
                         else if (g == 0) tap = 8, ci = j;
-                        else if (g < 3) tap = 4 * (g - 1) + j / 2, ci = 8 + j % 2;
-                        else if (j < 2) tap = 8, ci = 8 + j;
+                        else if (j / 2 != 2) tap = 3 * (g - 1) + (j / 2 == 3 ? 2 : j / 2), ci = 8 + j % 2;
                         if (tap < 0) continue;
                         const float w = W[((size_t)co * 10 + ci) * 9 + tap];
                         const _Float16 w0 = (_Float16)w;
