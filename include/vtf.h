@@ -197,6 +197,42 @@ int vtf_vit_encode_crops(vtf_vit_t h, const uint8_t* d_frames, int F, int H, int
 int vtf_gemm_split(const float* d_a, const float* d_b, int64_t M, int N, int K, const float* d_bias, float* d_out,
                    void* hip_stream);
 
+/* One convolution of the implicit-GEMM conv engine (csrc/conv.hip, conv_dma.hip) on dense fp32
+ * device buffers: the direct entry the kernel tests use.  The call packs the operands into the
+ * layout of `mode`, launches what production dispatch picks (path 0) or the named kernel
+ * configuration, and decodes the outputs to fp32.  Output buffers are read, taken through the
+ * kernel's layout and written back, never cleared: pre-fill them.
+ *   d_in  [N][H][W][in_cstride or Cin], d_w [Cout][KH][KW][Cin]
+ *   d_out [N][OH][OW][out_cstride] ([N][2 OH][2 OW][out_cstride] with up2)
+ *   ovf   host int32: 1 when a split-fp16 producer met |x| >= 2^14 (f16x / sp modes)
+ *   plan  host int32[8]: kernel id (0: nothing launched), BM, BN, dp_tiles, tail_split, split,
+ *         parts, cg of what ran (the ids are `path`'s values)
+ * Stream-ordered; returns after the stream is synchronised. */
+enum { VTF_CONV_FP32 = 0, VTF_CONV_F16X = 1, VTF_CONV_SP = 2, VTF_CONV_BF16 = 3, VTF_CONV_S3 = 4 };
+typedef struct vtf_conv2d_opts {
+    const float* bias;  /* device [Cout] or null */
+    const float* alpha; /* device [Cout] or null: v = fmaf(v, alpha, beta) */
+    const float* beta;
+    const float* prelu; /* device [Cout] or null */
+    const float* res;   /* device dense fp32 [N][OH][OW][Cout] ([N][OH/2][OW/2][Cout] with res_up2) or null */
+    float* out2;        /* device dense fp32 [N][OH][OW][out2_cstride] (n_split), pre-filled */
+    float* pool_out;    /* device dense fp32 [N][POH][POW][Cout] (pool_k > 0), pre-filled */
+    float scale, slope; /* scale 1 = off */
+    int32_t relu, leaky, gelu, res_post, res_up2, up2;
+    int32_t in_cstride, out_cstride, out_coff;
+    int32_t n_split, out2_cstride, out2_coff;
+    int32_t out_f32, split_fp32, out_sp;
+    int32_t mode;       /* VTF_CONV_* */
+    int32_t path;       /* 0 auto; 1-6 k_conv 128x32x32, 128x64x32 (fp32 / f16x), 64x32x64, 64x64x64,
+                         * 32x32x64, 32x64x64 (bf16); 10-13 k_conv_dma bf16 256x32, 256x64, 128x128,
+                         * 64x64 3-stage; 20-21 k_conv_dma split pairs 128x64, 128x128; 30 k_conv_span;
+                         * 31 k_conv_span_pool (plan only); 40-41 k_conv_dma3 128x64, 64x128 */
+    int32_t pool_k, pool_s; /* pool_k > 0: MaxPool2d(k, s, ceil_mode) after the conv (sp mode) */
+    int32_t pool_fused;     /* 1: launch_conv_span_pool (d_out may be null); 0: the conv, then launch_maxpool_ks_sp */
+} vtf_conv2d_opts;
+int vtf_conv2d(const float* d_in, const float* d_w, int N, int H, int W, int Cin, int Cout, int KH, int KW, int sh, int sw,
+               int ph, int pw, const vtf_conv2d_opts* opts, float* d_out, int32_t* ovf, int32_t* plan, void* hip_stream);
+
 /* ---------------------------------------------------------------- grouping
  * remove_dupes_overall 'enc' branch (dupes.py:51-68 with sklearn cosine_distances):
  * for each row i, min and argmin over j < i of clip(1 - cos(X_i, X_j), 0, 2); row 0 gets

@@ -471,7 +471,7 @@ static int pick_split(int64_t tiles, int KT, bool bf16, bool fp32_split) {
 }
 
 template <typename T, int BM, int BN, int BK>
-static void launch_tile(const ConvParams& p0, hipStream_t st) {
+static void launch_tile(const ConvParams& p0, hipStream_t st, ConvPlan* plan) {
     ConvParams p = p0;
     const int64_t gx = cdiv(p.M, BM), gy = cdiv(p.Cout, BN);
     const int KT = (p.K + BK - 1) / BK;
@@ -479,6 +479,12 @@ static void launch_tile(const ConvParams& p0, hipStream_t st) {
     p.ws = nullptr;
     if (p.split > 1) p.ws = splitk_workspace(st, (size_t)p.split * p.M * p.Cout * sizeof(float));
     p.group_m = conv_group_m();
+    if (plan) {
+        const int id = sizeof(T) == 4 ? (BN == 32 ? CK_K_128x32x32 : CK_K_128x64x32)
+                                      : (BM == 64 ? (BN == 32 ? CK_K_64x32x64 : CK_K_64x64x64)
+                                                  : (BN == 32 ? CK_K_32x32x64 : CK_K_32x64x64));
+        *plan = ConvPlan{id, BM, BN, (int)(gx * gy), 1, p.split, 0, 0};
+    }
 #if VTF_CONV_XDBG
     static const int xdbg = [] {
         const char* e = std::getenv("VTF_CONV_XDBG");
@@ -510,7 +516,19 @@ static void launch_tile(const ConvParams& p0, hipStream_t st) {
 }
 
 template <typename T>
-static void launch_t(const ConvParams& p, hipStream_t st) {
+static void launch_t(const ConvParams& p, hipStream_t st, int force, ConvPlan* plan) {
+    if (force != CK_AUTO) {
+        if constexpr (sizeof(T) == 2) {
+            if (force == CK_K_64x32x64) return launch_tile<T, 64, 32, 64>(p, st, plan);
+            if (force == CK_K_64x64x64) return launch_tile<T, 64, 64, 64>(p, st, plan);
+            if (force == CK_K_32x32x64) return launch_tile<T, 32, 32, 64>(p, st, plan);
+            if (force == CK_K_32x64x64) return launch_tile<T, 32, 64, 64>(p, st, plan);
+        } else {
+            if (force == CK_K_128x32x32) return launch_tile<T, 128, 32, 32>(p, st, plan);
+            if (force == CK_K_128x64x32) return launch_tile<T, 128, 64, 32>(p, st, plan);
+        }
+        VTF_CHECK(false, VTF_E_ARG, "conv: no such k_conv tile for this operand type");
+    }
     // bf16: 64-row tiles throughout -- measured on FaceNet (batch 128), twice the workgroups of
     // 128-row tiles hide more load latency than the larger tiles save in operand traffic
     // (forward 2.82 -> 2.67 ms); the per-output k order does not depend on the tile shape.
@@ -520,26 +538,27 @@ static void launch_t(const ConvParams& p, hipStream_t st) {
         const int64_t wg64 = (int64_t)cdiv(p.M, 64) * cdiv(p.Cout, BN);
         if (wg64 < (int64_t)conv_small_wg_per_cu() * device_cus()) {
             if (BN == 32)
-                launch_tile<T, 32, 32, 64>(p, st);
+                launch_tile<T, 32, 32, 64>(p, st, plan);
             else
-                launch_tile<T, 32, 64, 64>(p, st);
+                launch_tile<T, 32, 64, 64>(p, st, plan);
             return;
         }
     }
     if (p.Cout <= 32) {
         if constexpr (sizeof(T) == 2)
-            launch_tile<T, 64, 32, 64>(p, st);
+            launch_tile<T, 64, 32, 64>(p, st, plan);
         else
-            launch_tile<T, 128, 32, 32>(p, st);
+            launch_tile<T, 128, 32, 32>(p, st, plan);
     } else {
         if constexpr (sizeof(T) == 2)
-            launch_tile<T, 64, 64, 64>(p, st);
+            launch_tile<T, 64, 64, 64>(p, st, plan);
         else
-            launch_tile<T, 128, 64, 32>(p, st);
+            launch_tile<T, 128, 64, 32>(p, st, plan);
     }
 }
 
-void launch_conv(const ConvParams& p, bool bf16, hipStream_t st) {
+void launch_conv(const ConvParams& p, bool bf16, hipStream_t st, int force, ConvPlan* plan) {
+    if (plan) *plan = ConvPlan{};
     if (p.M <= 0) return;
     VTF_CHECK(p.Cin % 8 == 0, VTF_E_ARG, "conv: Cin must be a multiple of 8 (pad the input)");
     VTF_CHECK(p.in_cstride == 0 || (p.in_cstride >= p.Cin && p.in_cstride % 8 == 0), VTF_E_ARG,
@@ -553,14 +572,18 @@ void launch_conv(const ConvParams& p, bool bf16, hipStream_t st) {
         const char* e = std::getenv("VTF_CONV_DMA");
         return !(e && std::atoi(e) == 0);
     }();
-    if (bf16 && dma && conv_dma_choice_bf16(p) != 0) {
-        launch_conv_dma(p, true, st);
+    if (force >= CK_DMA0_256x32) {
+        launch_conv_dma(p, bf16, st, force, plan);
+        return;
+    }
+    if (force == CK_AUTO && bf16 && dma && conv_dma_choice_bf16(p) != 0) {
+        launch_conv_dma(p, true, st, CK_AUTO, plan);
         return;
     }
     if (bf16)
-        launch_t<__bf16>(p, st);
+        launch_t<__bf16>(p, st, force, plan);
     else
-        launch_t<float>(p, st);
+        launch_t<float>(p, st, force, plan);
 }
 
 // ---------------------------------------------------------------- maxpool 3x3 / 2, no padding (NHWC)

@@ -54,7 +54,37 @@ struct ConvParams {
     int out2_cstride, out2_coff;
 };
 
-void launch_conv(const ConvParams& p, bool bf16, hipStream_t st);
+// What one conv launch ran (vtf_conv2d reports it, so a test can assert the branch it meant to
+// hit): kernel = a ConvKernel id (0: nothing launched), its tile, conv_dma's whole tiles /
+// slices per tail tile, k_conv's split-K factor, the fused pool's bands per image / images per tile.
+struct ConvPlan {
+    int kernel, BM, BN, dp_tiles, tail_split, split, parts, cg;
+};
+// kernel configurations by name: ConvPlan::kernel, and the `force` argument of launch_conv /
+// launch_conv_dma (CK_AUTO = the production choice)
+enum ConvKernel {
+    CK_AUTO = 0,
+    CK_K_128x32x32 = 1,  // k_conv, fp32 / f16x operands
+    CK_K_128x64x32 = 2,
+    CK_K_64x32x64 = 3,  // k_conv, bf16 operands
+    CK_K_64x64x64 = 4,
+    CK_K_32x32x64 = 5,
+    CK_K_32x64x64 = 6,
+    CK_DMA0_256x32 = 10,  // k_conv_dma MODE 0 (bf16)
+    CK_DMA0_256x64 = 11,
+    CK_DMA0_128x128 = 12,
+    CK_DMA0_64x64x3 = 13,
+    CK_DMA1_128x64 = 20,  // k_conv_dma MODE 1 (split pairs)
+    CK_DMA1_128x128 = 21,
+    CK_SPAN = 30,       // k_conv_span (Q = Cin / 32)
+    CK_SPAN_POOL = 31,  // k_conv_span_pool
+    CK_DMA3_128x64 = 40,  // k_conv_dma3 (bf16x3)
+    CK_DMA3_64x128 = 41,
+};
+
+// force != CK_AUTO runs that configuration whatever the heuristics (CU count, once-read
+// environment switches) would pick; plan, when given, receives what was launched
+void launch_conv(const ConvParams& p, bool bf16, hipStream_t st, int force = CK_AUTO, ConvPlan* plan = nullptr);
 // VTF_NO_SPLITK=1 (read per launch): no conv splits K into slices, so every output is one
 // k-ordered MFMA chain (the fused FaceNet blocks' order: the bit-identity test's reference path)
 bool splitk_disabled();
@@ -62,11 +92,12 @@ bool splitk_disabled();
 bool conv_dma_ok(const ConvParams& p);
 // bf16 layer -> 0 k_conv, 1 conv_dma large tiles, 2 conv_dma 64 x 64 3-stage tiles (measured per shape)
 int conv_dma_choice_bf16(const ConvParams& p);
-void launch_conv_dma(const ConvParams& p, bool bf16, hipStream_t st);
+void launch_conv_dma(const ConvParams& p, bool bf16, hipStream_t st, int force = CK_AUTO, ConvPlan* plan = nullptr);
 // split-pair conv (bias + PReLU) fused with MaxPool2d(k, s, ceil_mode=True) writing the pooled map
 // in split pairs (conv_dma.hip, k_conv_span_pool); returns false, launching nothing, when the
 // shape does not fit the fused tiles (env VTF_CONV_SPAN_POOL=0: never)
-bool launch_conv_span_pool(ConvParams p, int k, int s, void* pout, int& POH, int& POW, hipStream_t st);
+bool launch_conv_span_pool(ConvParams p, int k, int s, void* pout, int& POH, int& POW, hipStream_t st,
+                           ConvPlan* plan = nullptr);
 void launch_maxpool(const void* in, int N, int H, int W, int C, void* out, int out_cstride, int out_coff, bool bf16,
                     hipStream_t st);
 // torch MaxPool2d(k, s, ceil_mode) without padding, NHWC fp32; returns (OH, OW)

@@ -1072,7 +1072,7 @@ int dma_group_m() {
 }
 
 template <int MODE, int BM, int BN, int WGM, int OCC = 2, int NSTG = 2>
-void launch_dma_t(ConvParams p, hipStream_t st) {
+void launch_dma_t(ConvParams p, hipStream_t st, ConvPlan* plan, int id) {
     using C = DCfg<MODE, BM, BN, WGM, OCC, NSTG>;
     p.gx = (int)cdiv(p.M, BM);
     p.gy = (int)cdiv(p.Cout, BN);
@@ -1102,13 +1102,14 @@ void launch_dma_t(ConvParams p, hipStream_t st) {
         }
     }
     const int nt = T - p.dp_tiles;
+    if (plan) *plan = ConvPlan{id, BM, BN, p.dp_tiles, p.tail_split, 1, 0, 0};
     p.ws = nt ? dma_ws(st, (size_t)nt * p.tail_split * BM * BN * 4) : nullptr;
     k_conv_dma<MODE, BM, BN, WGM, OCC, NSTG><<<(unsigned)(p.dp_tiles + nt * p.tail_split), 256, 0, st>>>(p);
     if (nt) k_conv_dma_tail<MODE, BM, BN, WGM, OCC, NSTG><<<(unsigned)(nt * (BM / 16) * (BN > 64 ? BN / 64 : 1)), 256, 0, st>>>(p);
 }
 
 template <int Q, int BM, int BN, int WGM, int SPAN, int OCC, int NS>
-void launch_span_t(ConvParams p, hipStream_t st) {
+void launch_span_t(ConvParams p, hipStream_t st, ConvPlan* plan) {
     p.gx = (int)cdiv(p.M, BM);
     p.gy = (int)cdiv(p.Cout, BN);
     p.group_m = dma_group_m();
@@ -1117,6 +1118,7 @@ void launch_span_t(ConvParams p, hipStream_t st) {
     p.tail_split = 1;
     p.split = 1;
     p.ws = nullptr;
+    if (plan) *plan = ConvPlan{CK_SPAN, BM, BN, p.dp_tiles, 1, 1, 0, 0};
     k_conv_span<Q, BM, BN, WGM, SPAN, OCC, NS><<<(unsigned)p.dp_tiles, 256, 0, st>>>(p);
 }
 
@@ -1124,12 +1126,15 @@ void launch_span_t(ConvParams p, hipStream_t st) {
 // (the swizzle pairs need odd row jumps), whose
 // tiles' input runs fit the LDS span); env VTF_CONV_SPAN=0 keeps the implicit-GEMM gather
 constexpr int SPAN_BM = 128, SPAN_ROWS = 240;
-bool conv_span_ok(const ConvParams& p) {
-    const char* e = std::getenv("VTF_CONV_SPAN");  // read per launch: tests A/B both paths in one process
-    return (!e || std::atoi(e) != 0) && p.in_sp && !p.s3 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 &&
+bool conv_span_fits(const ConvParams& p) {
+    return p.in_sp && !p.s3 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 &&
            (p.Cin == 32 || p.Cin == 64) && (p.in_cstride == 0 || p.in_cstride == p.Cin) && p.Cout <= 64 &&
            p.KH * p.KW >= 4 && (p.KW & 1) && !p.n_split && !p.res && !p.up2 && !p.res_up2 &&
            conv_span_max(p, SPAN_BM) <= SPAN_ROWS;
+}
+bool conv_span_ok(const ConvParams& p) {
+    const char* e = std::getenv("VTF_CONV_SPAN");  // read per launch: tests A/B both paths in one process
+    return (!e || std::atoi(e) != 0) && conv_span_fits(p);
 }
 
 // VTF_DMA3_WIDE_TAIL=1 (read per launch): bf16x3 convs also split last rounds of more than half
@@ -1141,7 +1146,7 @@ bool dma3_wide_tail() {
 }
 
 template <int BM, int BN, int WGM>
-void launch_dma3_t(ConvParams p, hipStream_t st) {
+void launch_dma3_t(ConvParams p, hipStream_t st, ConvPlan* plan) {
     p.gx = (int)cdiv(p.M, BM);
     p.gy = (int)cdiv(p.Cout, BN);
     p.group_m = dma_group_m();
@@ -1185,6 +1190,7 @@ void launch_dma3_t(ConvParams p, hipStream_t st) {
         }
     }
     const int nt = T - p.dp_tiles;
+    if (plan) *plan = ConvPlan{BM == 128 ? CK_DMA3_128x64 : CK_DMA3_64x128, BM, BN, p.dp_tiles, p.tail_split, 1, 0, 0};
     p.ws = nt ? dma_ws(st, (size_t)nt * p.tail_split * BM * BN * 4) : nullptr;
     k_conv_dma3<BM, BN, WGM><<<(unsigned)(p.dp_tiles + nt * p.tail_split), 256, 0, st>>>(p);
     // the slab layout (wave, fragment, lane) is MODE 1's for the same tile / wave grid
@@ -1200,7 +1206,8 @@ void release_dma_ws(hipStream_t st) { release_dma_ws_impl(st); }
 // conv (split pairs, bias + PReLU) + MaxPool2d(k, s, ceil_mode=True) in one launch
 // (k_conv_span_pool); false (nothing launched) when the shape does not fit its tiles
 constexpr int SPOOL_BM = 256, SPOOL_SPAN = 368;
-bool launch_conv_span_pool(ConvParams p, int k, int s, void* pout, int& POH, int& POW, hipStream_t st) {
+bool launch_conv_span_pool(ConvParams p, int k, int s, void* pout, int& POH, int& POW, hipStream_t st, ConvPlan* plan) {
+    if (plan) *plan = ConvPlan{};
     const char* e = std::getenv("VTF_CONV_SPAN_POOL");
     if ((e && std::atoi(e) == 0) || !p.in_sp || p.s3 || p.sh != 1 || p.sw != 1 || p.ph || p.pw || p.Cin != 32 ||
         (p.in_cstride && p.in_cstride != p.Cin) || p.Cout > 64 || p.Cout % 8 || !(p.KW & 1) || p.res || p.up2 ||
@@ -1236,6 +1243,7 @@ bool launch_conv_span_pool(ConvParams p, int k, int s, void* pout, int& POH, int
     if (span > SPOOL_SPAN || sp.cg * sp.RP * p.OW > SPOOL_BM) return false;
     p.zero = zero_page(stream_device(st));
     const int grid = sp.parts == 1 ? (int)cdiv(p.N, sp.cg) : p.N * sp.parts;
+    if (plan) *plan = ConvPlan{CK_SPAN_POOL, SPOOL_BM, 64, grid, 1, 1, sp.parts, sp.cg};
     // B stages (VTF_SPOOL_NS, experiments): 2 / 3 / 4 measured 288 / 292 / 295 us per launch on
     // c2 (the weight round trip is not what bounds it)
     static const int ns = [] {
@@ -1281,24 +1289,41 @@ int conv_dma_choice_bf16(const ConvParams& p) {
     return 0;
 }
 
-void launch_conv_dma(const ConvParams& p, bool bf16, hipStream_t st) {
+void launch_conv_dma(const ConvParams& p, bool bf16, hipStream_t st, int force, ConvPlan* plan) {
+    if (plan) *plan = ConvPlan{};
     if (p.M <= 0) return;
     VTF_CHECK(conv_dma_ok(p), VTF_E_ARG, "conv_dma: channel counts / strides must be multiples of 8");
     if (p.s3) {
+        VTF_CHECK(force == CK_AUTO || force == CK_DMA3_128x64 || force == CK_DMA3_64x128, VTF_E_ARG,
+                  "conv_dma: not a bf16x3 configuration");
         // bf16x3: 128 x 64 tiles up to 64 output channels, 64 x 128 above
-        if (p.Cout <= 64)
-            launch_dma3_t<128, 64, 2>(p, st);
+        if (force == CK_AUTO ? p.Cout <= 64 : force == CK_DMA3_128x64)
+            launch_dma3_t<128, 64, 2>(p, st, plan);
         else
-            launch_dma3_t<64, 128, 2>(p, st);
+            launch_dma3_t<64, 128, 2>(p, st, plan);
         return;
     }
     VTF_CHECK(bf16 || p.in_sp, VTF_E_ARG, "conv_dma: bf16 or split-pair operands");
     VTF_CHECK(!p.out_sp || !bf16, VTF_E_ARG, "conv_dma: split-pair output is an fp32-mode output");
+    if (force != CK_AUTO) {
+        // a named configuration (vtf_conv2d): the tile templates below, picked directly
+        if (bf16 && force == CK_DMA0_256x32) return launch_dma_t<0, 256, 32, 4>(p, st, plan, force);
+        if (bf16 && force == CK_DMA0_256x64) return launch_dma_t<0, 256, 64, 4>(p, st, plan, force);
+        if (bf16 && force == CK_DMA0_128x128) return launch_dma_t<0, 128, 128, 2>(p, st, plan, force);
+        if (bf16 && force == CK_DMA0_64x64x3) return launch_dma_t<0, 64, 64, 2, 3, 3>(p, st, plan, force);
+        if (!bf16 && force == CK_DMA1_128x64) return launch_dma_t<1, 128, 64, 2, 3>(p, st, plan, force);
+        if (!bf16 && force == CK_DMA1_128x128) return launch_dma_t<1, 128, 128, 2>(p, st, plan, force);
+        if (!bf16 && force == CK_SPAN && conv_span_fits(p)) {
+            if (p.Cin == 32) return launch_span_t<1, SPAN_BM, 64, 2, SPAN_ROWS, 3, 2>(p, st, plan);
+            return launch_span_t<2, SPAN_BM, 64, 2, SPAN_ROWS, 2, 2>(p, st, plan);
+        }
+        VTF_CHECK(false, VTF_E_ARG, "conv_dma: the named configuration does not fit this conv");
+    }
     if (bf16) {
         // grids below a whole round of large tiles (FaceNet Block35 / 17 / 8): 64 x 64 tiles, three
         // stages (two k-steps in flight) at 3 workgroups per CU
         if (conv_dma_choice_bf16(p) == 2) {
-            launch_dma_t<0, 64, 64, 2, 3, 3>(p, st);
+            launch_dma_t<0, 64, 64, 2, 3, 3>(p, st, plan, CK_DMA0_64x64x3);
             return;
         }
         // Cout an odd multiple of 64 (FaceNet's 192-channel convs): 256 x 64 tiles instead of 128 x
@@ -1310,11 +1335,11 @@ void launch_conv_dma(const ConvParams& p, bool bf16, hipStream_t st) {
         }();
         const bool n64 = n64_on && p.Cout % 128 != 0 && p.Cout % 64 == 0;
         if (p.Cout <= 32)
-            launch_dma_t<0, 256, 32, 4>(p, st);
+            launch_dma_t<0, 256, 32, 4>(p, st, plan, CK_DMA0_256x32);
         else if (p.Cout <= 64 || n64)
-            launch_dma_t<0, 256, 64, 4>(p, st);
+            launch_dma_t<0, 256, 64, 4>(p, st, plan, CK_DMA0_256x64);
         else
-            launch_dma_t<0, 128, 128, 2>(p, st);
+            launch_dma_t<0, 128, 128, 2>(p, st, plan, CK_DMA0_128x128);
     } else {
         // split mode, <= 64 channels (MTCNN RNet / ONet convs, K = 192..576: 6-18 k-steps, so the
         // per-tile prologue / epilogue latency weighs): 128 x 64 tiles at 3 workgroups per CU hide
@@ -1325,21 +1350,21 @@ void launch_conv_dma(const ConvParams& p, bool bf16, hipStream_t st) {
         }();
         if (conv_span_ok(p)) {
             if (p.Cin == 32)
-                launch_span_t<1, SPAN_BM, 64, 2, SPAN_ROWS, 3, 2>(p, st);
+                launch_span_t<1, SPAN_BM, 64, 2, SPAN_ROWS, 3, 2>(p, st, plan);
             else
-                launch_span_t<2, SPAN_BM, 64, 2, SPAN_ROWS, 2, 2>(p, st);
+                launch_span_t<2, SPAN_BM, 64, 2, SPAN_ROWS, 2, 2>(p, st, plan);
             return;
         }
         if (p.Cout <= 64 && big == 256)
-            launch_dma_t<1, 256, 64, 4>(p, st);
+            launch_dma_t<1, 256, 64, 4>(p, st, plan, CK_AUTO);
         else if (p.Cout <= 64 && big == 64)
-            launch_dma_t<1, 64, 64, 2, 3, 3>(p, st);
+            launch_dma_t<1, 64, 64, 2, 3, 3>(p, st, plan, CK_AUTO);
         else if (p.Cout <= 64 && big == 129)
-            launch_dma_t<1, 128, 64, 2, 2, 3>(p, st);
+            launch_dma_t<1, 128, 64, 2, 2, 3>(p, st, plan, CK_AUTO);
         else if (p.Cout <= 64)
-            launch_dma_t<1, 128, 64, 2, 3>(p, st);
+            launch_dma_t<1, 128, 64, 2, 3>(p, st, plan, CK_DMA1_128x64);
         else
-            launch_dma_t<1, 128, 128, 2>(p, st);
+            launch_dma_t<1, 128, 128, 2>(p, st, plan, CK_DMA1_128x128);
     }
 }
 

@@ -55,6 +55,7 @@ SIGNATURES = {
     'vtf_vit_encode_crops': [_p, _p, _i32, _i32, _i32, _i64, _i64, _p, _i32, _i64, _p],
     'vtf_blob_from_crops': [_p, _i32, _i32, _i32, _i64, _i64, _p, _i64, _i32, _f32, _f32, _p, _p],
     'vtf_gemm_split': [_p, _p, _i64, _i32, _i32, _p, _p, _p],
+    'vtf_conv2d': [_p, _p] + [_i32] * 11 + [_p, _p, _p, _p, _p],
     'vtf_cosine_dedupe': [_p, _i64, _i64, _p, _p, _p],
     'vtf_cosine_dedupe_rows': [_p, _i64, _i64, _i64, _i64, _p, _p, _p],
     'vtf_group_create': [_i32, _p],
@@ -127,6 +128,19 @@ class BoxParams(ctypes.Structure):
             scale = (scale,) * 4
         return cls(float(mscore), float(msize), float(mborder or 0), (_c.c_double * 4)(*[float(v) for v in scale]),
                    1 if square else 0, 1 if adjust else 0)
+
+
+class Conv2dOpts(ctypes.Structure):
+    """vtf_conv2d_opts (include/vtf.h): epilogue, layout, operand mode and kernel path of vtf_conv2d."""
+    _fields_ = ([(n, _p) for n in ('bias', 'alpha', 'beta', 'prelu', 'res', 'out2', 'pool_out')] +
+                [('scale', _f32), ('slope', _f32)] +
+                [(n, _c.c_int32) for n in ('relu', 'leaky', 'gelu', 'res_post', 'res_up2', 'up2', 'in_cstride',
+                                           'out_cstride', 'out_coff', 'n_split', 'out2_cstride', 'out2_coff',
+                                           'out_f32', 'split_fp32', 'out_sp', 'mode', 'path', 'pool_k', 'pool_s',
+                                           'pool_fused')])
+
+
+CONV_MODES = {'fp32': 0, 'f16x': 1, 'sp': 2, 'bf16': 3, 's3': 4}
 
 
 def lib():
